@@ -11,6 +11,16 @@ one-sidedly (HIP-IPC over xGMI).
     python bench.py                                   # N=1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the last step's outputs, DIR/*.npy
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, print.
+What is measured beside it belongs behind --full.  Today that is the per-layer kernel tuning
+(hipps.ops.nn.TUNER: every candidate of every conv / GEMM shape timed during the first step, the
+MIOpen candidates with an algorithm search each, 20-25 s in all): a plain one-GPU run adopts the
+choices recorded in bench/tuner_picks.json (measured once on an MI355X by the command below) and
+measures only keys the file lacks; --full (or
+--tuner-picks measure) measures them all in-process.  After kernel work, regenerate the file:
+    python bench.py --full --save-tuner-picks bench/tuner_picks.json
 
 Timing: W warmup steps, then barrier + synchronize, K timed steps, barrier + synchronize; the
 per-rank elapsed time is max-reduced; rank 0 prints one JSON line.  value = whole-job samples/s
@@ -79,6 +89,25 @@ def parse():
                     help="let MIOpen use its non-deterministic convolution algorithms (default: "
                          "hipps.set_deterministic, bit-for-bit repeatable steps at no measured cost)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy "
+                         "(float32): loss.npy, the step's loss, and params.npy, the model parameters after the step "
+                         "(every parameter in order; a fixed seeded sample of the large ones, see _dump_outputs). "
+                         "Seeds, inputs and the sample are functions of the arguments alone, so two builds can be "
+                         "compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the benchmark measures beside its headline figure.  Today that is the per-layer "
+                         "kernel tuning: with --full every kernel choice is measured in this process during the first "
+                         "step (20-25 s of candidate timings and MIOpen algorithm searches before the first step "
+                         "ends), as a training script does; a plain N=1 run adopts the choices recorded in "
+                         "bench/tuner_picks.json (--tuner-picks) and measures only the keys the file lacks")
+    ap.add_argument("--tuner-picks", default="auto", metavar="auto|measure|FILE",
+                    help="kernel choices (hipps.ops.nn.TUNER): 'auto' (default) = bench/tuner_picks.json for a plain "
+                         "one-GPU run, measured in-process with --full or at N > 1; 'measure' = always measured; "
+                         "FILE = picks written by --save-tuner-picks")
+    ap.add_argument("--save-tuner-picks", default=None, metavar="FILE",
+                    help="write every kernel choice this run made or adopted as JSON (regenerate the recorded "
+                         "file after kernel work: python bench.py --full --save-tuner-picks bench/tuner_picks.json)")
     ap.add_argument("--no-fallback", action="store_true",
                     help="fail if the ps_async IPC transport refuses to initialise (default: when the driver call "
                          "returned an error, run the SAME async PS over its p2p transport -- RCCL pair send/recv -- "
@@ -98,6 +127,54 @@ def parse():
                     help="N=1 rehearsal of the co-located PS at N=1+E: the PS also accumulates E emulated remote "
                          "messages per step and sweeps their push / pull bytes (PSConfig.emulate_remote)")
     return ap.parse_args()
+
+
+PICKS_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bench", "tuner_picks.json")
+
+
+def _load_picks(tuner, path):
+    """Adopt recorded kernel choices (JSON list of [key, candidate name]; keys hold nested tuples,
+    stored as lists).  A recorded key wins over measuring; keys not in the file are measured as
+    usual.  Returns the number adopted."""
+    def tup(v):
+        return tuple(tup(i) for i in v) if isinstance(v, list) else v
+
+    with open(path) as f:
+        picks = json.load(f)
+    for k, v in picks:
+        tuner.cache[tup(k)] = v
+    return len(picks)
+
+
+def _save_picks(tuner, path):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        f.write("[\n" + ",\n".join(json.dumps([list(k), v]) for k, v in tuner.cache.items()) + "\n]\n")
+
+
+DUMP_SAMPLE = 16384 # elements kept of a parameter larger than this (ResNet-50: 161 tensors, < 7 MB in all)
+
+
+def _dump_outputs(path, loss, model):
+    """Write the last timed step's outputs as float32 .npy files: ``loss.npy`` (shape [1]) and
+    ``params.npy``, the concatenation over ``model.parameters()`` in order of each parameter
+    flattened -- whole if it has at most DUMP_SAMPLE elements, else its elements at DUMP_SAMPLE
+    indices drawn once from a generator seeded with 0 (the same indices in every run of the same
+    model).  The caller has synchronized the device."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    parts = []
+    for p in model.parameters():
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=gen)
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(path, "params.npy"), torch.cat(parts).numpy().astype(np.float32))
+    val = float("nan") if loss is None else float(loss.detach().float().item())
+    np.save(os.path.join(path, "loss.npy"), np.asarray([val], dtype=np.float32))
 
 
 def main():
@@ -127,6 +204,13 @@ def main():
     from hipps.models import build_model
 
     hipps.set_deterministic(not a.nondeterministic)
+    picks_from = None
+    if a.tuner_picks == "auto":
+        if N == 1 and not a.full and os.path.exists(PICKS_FILE):
+            picks_from = PICKS_FILE
+    elif a.tuner_picks != "measure":
+        picks_from = a.tuner_picks
+    n_picks = _load_picks(hnn.TUNER, picks_from) if picks_from else 0
 
     torch.manual_seed(1234 + world.rank)
     is_tf = a.model in TRANSFORMERS
@@ -332,6 +416,12 @@ def main():
     gran_eff = getattr(opt.engine, "granularity", None)
     ti = opt.engine.transport_info() if hasattr(opt.engine, "transport_info") else {}
     nparams = sum(p.numel() for p in model.parameters())
+    if a.dump_outputs and world.rank == 0:
+        opt.join_pull()  # (a split pull's late half may still be in flight on its side stream)
+        torch.cuda.synchronize()
+        _dump_outputs(a.dump_outputs, loss, model)
+    if a.save_tuner_picks and world.rank == 0:
+        _save_picks(hnn.TUNER, a.save_tuner_picks)
     opt.close()
     stats = {}
     if hasattr(opt, "_last_engine_stats"):
@@ -391,6 +481,8 @@ def main():
                              "npub": ti.get("npub"),
                              "rank0_budget_gb": ti.get("budget_gb")}
                             if mode == "ps_async" else None),
+                "tuner_picks": (f"recorded ({os.path.basename(picks_from)}: {n_picks} keys)" if picks_from
+                                else "measured in-process"),
                 "python_gc": a.gc,
                 "deterministic": not a.nondeterministic,
                 "wgrad_join": ("deferred" if mode == "ps_async" and not a.no_defer_wgrad_join else "end of backward"),

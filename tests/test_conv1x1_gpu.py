@@ -379,11 +379,21 @@ def test_bn_relu_prologue_matches_materialized(cin, cout, hw):
     assert torch.equal(dwa, dwb)
 
 
-def test_bottleneck_bn2_prologue_matches_apply_path():
+def test_bottleneck_bn2_prologue_matches_apply_path(monkeypatch):
     """ResNet bottlenecks with bn2's apply in conv3's operand prologue vs the apply-kernel path:
-    forward output and every gradient agree (the prologue recomputes the same bf16 values)."""
+    forward output and every gradient agree (the prologue recomputes the same bf16 values).
+
+    The per-layer tuner route (bn_pro_pays) is held off for both runs: its pick for these shapes is
+    a timing made once per process, possibly by an earlier test, and when it says 'pro' the
+    reference run is no longer the apply-kernel path but a third one (the in-LDS prologue of
+    gemm2, whose BN statistics come from the GEMM epilogue's partials and differ from the reduced
+    ones in the last fp32 bits).  A handful of bf16 roundings and ReLU bits then flip, each worth a
+    few per cent of a gradient row here -- the same distance from fp32 for all three paths (relative
+    L2 error of x.grad 0.1887 for each), but not the element-wise agreement this test asserts of
+    the two paths it names.  The tuned route has its own comparison (test_fused_bn.py)."""
     import hipps.models.resnet as R
 
+    monkeypatch.setattr(R, "bn_pro_pays", lambda *a: False)
     torch.manual_seed(5)
     net = torch.nn.Sequential(R.Bottleneck(64, 64, stride=1, downsample=True), R.Bottleneck(256, 64),
                               R.Bottleneck(256, 128, stride=2, downsample=True))

@@ -20,6 +20,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ._native import native
+from .tuner import TUNER, _G2_TILES, _TUNE_QUIET, _Tuner, add_tune_quiet, remove_tune_quiet  # noqa: F401
+from .tuner import g2_names as _g2_names, g2_parse as _g2_parse, wgrad_names as _wgrad_names, wgrad_parse as _wgrad_parse
 
 import os as _os
 
@@ -237,116 +239,17 @@ def _on_wgrad_stream(param, tensors, fn):
     return out
 
 
-_TUNE_QUIET: list = []  # context-manager factories that keep other GPU work off while timing
-
-
-def add_tune_quiet(fn) -> None:
-    """Register ``fn() -> context manager`` to be entered around every tuner measurement (the
-    co-located async PS registers a pause of its thread: its kernels would otherwise share the GPU
-    with the timed candidates and skew the picks)."""
-    _TUNE_QUIET.append(fn)
-
-
-def remove_tune_quiet(fn) -> None:
-    if fn in _TUNE_QUIET:
-        _TUNE_QUIET.remove(fn)
-
-
-class _Tuner:
-    """Per-shape kernel choice by measurement (like cudnn.benchmark): on the first call for a
-    key, every candidate runs once to warm up; then, with the device drained and the registered
-    background work held (add_tune_quiet), ROUNDS rounds each time every candidate (2 calls between
-    HIP events, candidates interleaved) and the fastest by its best round is cached.  Interleaved
-    rounds and the minimum keep a transient neighbour (another stream's kernels) from deciding a
-    pick: with the co-located PS running free a measured 35 % slower set of weight-gradient
-    tilings was once picked (profiles/r5/emu/).  Candidates must be side-effect free apart from
-    writing their output (every candidate writes the same values)."""
-
-    ROUNDS = 3
-
-    def __init__(self):
-        self.cache: dict = {}
-        self.times: dict = {}
-
-    def pick(self, key, cands: dict) -> str:
-        got = self.cache.get(key)
-        if got is not None:
-            return got
-        if len(cands) == 1:
-            got = next(iter(cands))
-        else:
-            import contextlib
-
-            for fn in cands.values():
-                fn()
-            with contextlib.ExitStack() as quiet:
-                for q in list(_TUNE_QUIET):
-                    try:
-                        quiet.enter_context(q())
-                    except Exception:  # (a quiet hook that cannot hold: measure anyway)
-                        pass
-                # drain every stream first: kernels still running on another stream (the weight-
-                # gradient side stream, the PS stream) would otherwise share the GPU with the timing
-                torch.cuda.synchronize()
-                evs = {name: [] for name in cands}
-                for _ in range(self.ROUNDS):
-                    for name, fn in cands.items():
-                        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        s.record()
-                        fn()
-                        fn()
-                        e.record()
-                        evs[name].append((s, e))
-                torch.cuda.synchronize()
-            t = {name: min(s.elapsed_time(e) for s, e in pairs) / 2 for name, pairs in evs.items()}
-            got = min(t, key=t.get)
-            self.times[key] = t
-        self.cache[key] = got
-        return got
-
-    def save(self, path: str) -> None:
-        """Write every pick (key -> candidate name) as JSON."""
-        import json
-
-        with open(path, "w") as f:
-            json.dump([[list(k), v] for k, v in self.cache.items()], f)
-
-    def load(self, path: str) -> int:
-        """Adopt recorded picks (they win over measuring): runs that load the same file make the
-        same choices, so choices between candidates that are not bitwise equal (weight-gradient
-        slab counts, the BN prologue route) cannot differ between runs or ranks.  Returns the
-        number of picks loaded."""
-        import json
-
-        with open(path) as f:
-            for k, v in json.load(f):
-                self.cache[tuple(k)] = v
-        return len(self.cache)
-
-
-TUNER = _Tuner()
-# HIPPS_TUNER_CACHE=<file>: picks recorded by TUNER.save are loaded at import (set_deterministic)
-if _os.environ.get("HIPPS_TUNER_CACHE") and _os.path.exists(_os.environ["HIPPS_TUNER_CACHE"]):
-    TUNER.load(_os.environ["HIPPS_TUNER_CACHE"])
-# (block rows, block cols, LDS stages): 3 stages keep one tile's DMA in flight across every
-# K-loop barrier (gemm2.hip k_gemm NS).  Only 128x64 keeps two blocks per CU with 3 stages; the
-# others drop to one wave per SIMD and lose (profiles/gemm2_probe_r3_stages.json).  (256, 256, 5):
-# the ping-pong schedule of the 256x256 tile (gemm2.hip k_gemm NS == 5)
-_G2_TILES = ((128, 128, 2), (256, 256, 2), (256, 256, 5), (128, 64, 2), (256, 64, 2), (128, 64, 3))
-
-
-def _g2_names(N: int):
-    return [f"g2_{bm}x{bn}" + ("" if ns == 2 else f"s{ns}") for bm, bn, ns in _G2_TILES if N % bn == 0]
-
-
-def _g2_parse(name: str):
-    """'g2_256x128s3' -> (256, 128, 3); 'g2_128x64' -> (128, 64, 2)"""
-    t = name[3:]
-    ns = 2
-    if "s" in t:
-        t, ns = t.split("s")
-    bm, bn = (int(v) for v in t.split("x"))
-    return bm, bn, int(ns)
+def _bn_backward_after(C, dy, part, bg, c) -> None:
+    """Tuner timing: what a candidate that gave (dy, part) leaves the backward of the BN ``bg`` (BNGradTap,
+    ``c`` channels): its reduction pass over (dy, bn x) if part is None (MIOpen), else only the apply."""
+    mode = MASK_BITS if bg.mask is not None else MASK_X
+    dx, dgw, dgb = torch.empty_like(dy), torch.empty_like(bg.scale), torch.empty_like(bg.scale)
+    if part is None:
+        C.bn_backward(dy, bg.x, None, mode, bg.scale, bg.mean, bg.invstd, bg.scale, bg.shift, dx, None, dgw, dgb, c,
+                      bg.mask)
+    else:
+        C.bn_backward_partials(part, part.shape[2], dy, bg.x, mode, bg.scale, bg.mean, bg.invstd, bg.scale, bg.shift,
+                               dx, None, dgw, dgb, c, bg.mask)
 
 
 def _conv1x1_gemm(x2, w2d, y, Hi, Wi, stride, part_needed, add=None, add_mask=None, bg=None, add_s2=False):
@@ -384,8 +287,7 @@ def _conv1x1_gemm(x2, w2d, y, Hi, Wi, stride, part_needed, add=None, add_mask=No
     if _GEMM2 and K % 64 == 0 and N % 64 == 0:
         epi = (part_needed, add is not None, add_mask is not None, bg is not None and bg.mask is not None,
                bg is not None, add_s2)
-        name = TUNER.pick(("1x1", M, K, N, stride, Hi, Wi, epi),
-                          {n: (lambda n=n: run(n)) for n in ([] if add_s2 else ["g1"]) + _g2_names(N)})
+        name = TUNER.pick(("1x1", M, K, N, stride, Hi, Wi, epi), ([] if add_s2 else ["g1"]) + _g2_names(N), run)
     elif add_s2:
         raise RuntimeError("the compact stride-2 addend needs the gemm2 core")
     return run(name)
@@ -397,44 +299,28 @@ def _conv_wgrad(dy, x, dw, kh, kw, stride, pad):
     C = native()
     hi, wi = x.shape[2], x.shape[3]
     cout, cin = dy.shape[1], x.shape[1]
-    if kh == kw == 1 and pad == 0:
-        first = lambda: C.conv1x1_wgrad(dy, x, dw.view(cout, cin), hi, wi, stride)  # noqa: E731
-    else:
-        first = lambda: C.conv_wgrad(dy, x, dw, kh, kw, stride, pad)  # noqa: E731
-    def mio():  # MIOpen's bf16 weight gradient (the 64-channel KxK layers' previous route)
-        w = torch.empty((cout, cin, kh, kw), dtype=torch.bfloat16, device=dy.device)
-        g = torch.ops.aten.convolution_backward(dy, x, w, None, [stride, stride], [pad, pad], [1, 1], False, [0, 0], 1,
-                                                [False, True, False])[1]
-        dw.copy_(g)
+
+    def run(name):
+        if name == "w2":
+            if kh == kw == 1 and pad == 0:
+                C.conv1x1_wgrad(dy, x, dw.view(cout, cin), hi, wi, stride)
+            else:
+                C.conv_wgrad(dy, x, dw, kh, kw, stride, pad)
+        elif name == "miopen":  # MIOpen's bf16 weight gradient (the 64-channel KxK layers' previous route)
+            w = torch.empty((cout, cin, kh, kw), dtype=torch.bfloat16, device=dy.device)
+            g = torch.ops.aten.convolution_backward(dy, x, w, None, [stride, stride], [pad, pad], [1, 1], False,
+                                                    [0, 0], 1, [False, True, False])[1]
+            dw.copy_(g)
+        else:
+            C.gemm2_wgrad(dy, x, dw, kh, kw, stride, pad, hi, wi, *_wgrad_parse(name))
 
     name = "w2"
     if _GEMM2 and cout % 64 == 0 and cin % 64 == 0:
-        cands = {"w2": first}
-        # gemm2.hip k_wgrad tilings (Cout x Cin*taps outputs): 0 128x128 (4 waves), 1 256x128
-        # (4 waves), 2 256x256 (8 waves), 3 128x256 / 4 256x128 (8 waves of 64x64)
-        ok = {0: True, 1: cout % 256 == 0 and cin % 128 == 0, 2: cout % 256 == 0 and cin % 256 == 0,
-              3: cout % 128 == 0 and cin % 256 == 0, 4: cout % 256 == 0 and cin % 128 == 0}
-        # 5 / 6: 64-channel KxK layers, two taps per 128-wide tile (K padded): 2 / 4 waves
-        ok[5] = ok[6] = cin == 64 and kh * kw > 1
-        for cfg in (0, 1, 2, 3, 4, 5, 6):
-            if ok[cfg]:
-                # LDS stages (3 do not fit 256x256; 4 = 32-row k-half units, see gemm2.hip)
-                for ns in ((2, 3) if cfg != 2 else (2, 4)) + ((4,) if cfg == 0 else ()):
-                    cands[f"w3_{cfg}" + ("" if ns == 2 else f"s{ns}")] = (
-                        lambda cfg=cfg, ns=ns: C.gemm2_wgrad(dy, x, dw, kh, kw, stride, pad, hi, wi, cfg, ns))
-        # (fewer, longer M slabs -- gemm2_wgrad sdiv=2, half the fp32 slab traffic -- measured: no
-        # shape faster by more than 1 %, profiles/r3b/tuner_sdiv.json; not a candidate)
+        names = ["w2"] + _wgrad_names(cout, cin, kh * kw, "conv")
         if kh > 1 and cin < 128 and _MIOPEN_WGRAD:
-            cands["miopen"] = mio
-        name = TUNER.pick(("wgrad", tuple(x.shape), cout, kh, kw, stride, pad), cands)
-    if name.startswith("w3"):
-        sdiv = int(name.split("d")[1]) if "d" in name else 1
-        C.gemm2_wgrad(dy, x, dw, kh, kw, stride, pad, hi, wi, int(name[3]), int(name[5]) if len(name) > 4 else 2,
-                      sdiv=sdiv)
-    elif name == "miopen":
-        mio()
-    else:
-        first()
+            names.append("miopen")
+        name = TUNER.pick(("wgrad", tuple(x.shape), cout, kh, kw, stride, pad), names, run)
+    run(name)
 
 
 def _convkxk_gemm(x, w, stride, pad, stats: bool, bg=None):
@@ -448,11 +334,10 @@ def _convkxk_gemm(x, w, stride, pad, stats: bool, bg=None):
     cout, k = w.shape[0], w.shape[2]
     ho, wo = (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1
     y = torch.empty((n, cout, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-    mio = lambda: torch.ops.aten.convolution(x, w, None, [stride, stride], [pad, pad], [1, 1], False, [0, 0], 1)  # noqa: E731
 
     def run(name):
         if name == "miopen":
-            return mio(), None
+            return torch.ops.aten.convolution(x, w, None, [stride, stride], [pad, pad], [1, 1], False, [0, 0], 1), None
         bm, bn, ns = _g2_parse(name)
         part = None
         if stats or bg is not None:
@@ -478,20 +363,12 @@ def _convkxk_gemm(x, w, stride, pad, stats: bool, bg=None):
                 C.bn_finalize_partials(part, part.shape[2], n * ho * wo, v[0], v[1], None, None, v[2], v[3], v[4],
                                        v[5], cout, 1e-5, 0.1)
         if bg is not None:
-            mode = MASK_BITS if bg.mask is not None else MASK_X
-            dx, dgw, dgb = torch.empty_like(yy), torch.empty_like(bg.scale), torch.empty_like(bg.scale)
-            if part is None:
-                C.bn_backward(yy, bg.x, None, mode, bg.scale, bg.mean, bg.invstd, bg.scale, bg.shift, dx, None,
-                              dgw, dgb, cout, bg.mask)
-            else:
-                C.bn_backward_partials(part, part.shape[2], yy, bg.x, mode, bg.scale, bg.mean, bg.invstd, bg.scale,
-                                       bg.shift, dx, None, dgw, dgb, cout, bg.mask)
+            _bn_backward_after(C, yy, part, bg, cout)
 
     name = "miopen"
     if _GEMM2 and cin % 64 == 0 and cout % 64 == 0:
         epi = (stats, None if bg is None else bg.mask is not None)
-        name = TUNER.pick(("kxk", n, cin, h, wd, cout, k, stride, pad, epi),
-                          {nm: (lambda nm=nm: timed(nm)) for nm in ["miopen"] + _g2_names(cout)})
+        name = TUNER.pick(("kxk", n, cin, h, wd, cout, k, stride, pad, epi), ["miopen"] + _g2_names(cout), run, timed)
     return run(name)
 
 
@@ -504,13 +381,10 @@ def _dgrad_s2(dy, x, w, wf, bg=None):
     n, cin, h, wd = x.shape
     cout = dy.shape[1]
 
-    def mio():
-        return torch.ops.aten.convolution_backward(dy, x, w, None, [2, 2], [1, 1], [1, 1], False, [0, 0], 1,
-                                                   [True, False, False])[0], None
-
     def run(name):
         if name == "miopen":
-            return mio()
+            return torch.ops.aten.convolution_backward(dy, x, w, None, [2, 2], [1, 1], [1, 1], False, [0, 0], 1,
+                                                       [True, False, False])[0], None
         bm, bn, _ = _g2_parse(name)
         dx = torch.empty_like(x, memory_format=torch.channels_last)
         if bg is not None:
@@ -522,18 +396,10 @@ def _dgrad_s2(dy, x, w, wf, bg=None):
     def timed(name):
         dx, part = run(name)
         if bg is not None:
-            mode = MASK_BITS if bg.mask is not None else MASK_X
-            d2, dgw, dgb = torch.empty_like(dx), torch.empty_like(bg.scale), torch.empty_like(bg.scale)
-            if part is None:
-                C.bn_backward(dx, bg.x, None, mode, bg.scale, bg.mean, bg.invstd, bg.scale, bg.shift, d2, None, dgw,
-                              dgb, cin, bg.mask)
-            else:
-                C.bn_backward_partials(part, part.shape[2], dx, bg.x, mode, bg.scale, bg.mean, bg.invstd, bg.scale,
-                                       bg.shift, d2, None, dgw, dgb, cin, bg.mask)
+            _bn_backward_after(C, dx, part, bg, cin)
 
-    names = ["miopen"] + [nm for nm in ("g2_128x128", "g2_256x256", "g2_128x64", "g2_256x64") if cin % _g2_parse(nm)[1] == 0]
     name = TUNER.pick(("dgrad_s2", n, cin, h, wd, cout, None if bg is None else bg.mask is not None),
-                      {nm: (lambda nm=nm: timed(nm)) for nm in names})
+                      ["miopen"] + _g2_names(cin, 2), run, timed)
     return run(name)
 
 
@@ -555,9 +421,7 @@ def _conv_pro_fwd(x, w, stride, pad, scale, shift):
         C.gemm2_conv(x, w2, y, part, None, None, h, wd, stride, k, k, pad, bm, bn, pro_scale=scale, pro_shift=shift)
         return y, part
 
-    names = [nm for nm in _g2_names(cout) if _g2_parse(nm)[2] == 2]
-    name = TUNER.pick(("pro", n, cin, h, wd, cout, k, stride, pad), {nm: (lambda nm=nm: run(nm)) for nm in names})
-    return run(name)
+    return run(TUNER.pick(("pro", n, cin, h, wd, cout, k, stride, pad), _g2_names(cout, 2), run))
 
 
 def _conv_wgrad_pro(dy, x, dw, kh, kw, stride, pad, scale, shift):
@@ -566,12 +430,11 @@ def _conv_wgrad_pro(dy, x, dw, kh, kw, stride, pad, scale, shift):
     C = native()
     hi, wi = x.shape[2], x.shape[3]
     cout, cin = dy.shape[1], x.shape[1]
-    ok = {0: True, 1: cout % 256 == 0 and cin % 128 == 0, 3: cout % 128 == 0 and cin % 256 == 0,
-          4: cout % 256 == 0 and cin % 128 == 0, 5: cin == 64 and kh * kw > 1, 6: cin == 64 and kh * kw > 1}
-    cands = {f"w3_{cfg}": (lambda cfg=cfg: C.gemm2_wgrad(dy, x, dw, kh, kw, stride, pad, hi, wi, cfg, 2, scale, shift))
-             for cfg, v in ok.items() if v}
-    name = TUNER.pick(("wgrad_pro", tuple(x.shape), cout, kh, kw, stride, pad), cands)
-    cands[name]()
+
+    def run(name):
+        C.gemm2_wgrad(dy, x, dw, kh, kw, stride, pad, hi, wi, *_wgrad_parse(name), scale, shift)
+
+    run(TUNER.pick(("wgrad_pro", tuple(x.shape), cout, kh, kw, stride, pad), _wgrad_names(cout, cin, kh * kw, "pro"), run))
 
 
 class _BNReluConv(torch.autograd.Function):
@@ -689,8 +552,8 @@ def bn_pro_pays(bn, conv: nn.Conv2d, x, part) -> bool:
     n, c, h, wd = x.shape
     cout = conv.out_channels
     key = ("bnpro", n, c, h, wd, cout)
-    got = TUNER.cache.get(key)
-    if got is None:
+    got = TUNER.cache.get(key)  # (looked up here: a hit allocates none of the operands below)
+    if got not in ("apply", "pro"):
         C = native()
         cl = torch.channels_last
         w = bf16_weight(conv.weight)
@@ -704,19 +567,19 @@ def bn_pro_pays(bn, conv: nn.Conv2d, x, part) -> bool:
         dw = torch.empty((cout, c), **f32)
         eps, mom = float(bn.eps), float(bn.momentum)
 
-        def apply():
-            C.bn_forward_partials(part, part.shape[2], x, None, y, bn.weight, bn.bias, rm, rv, mean, invstd, scale,
-                                  shift, c, eps, mom, True, None)
-            _conv1x1_gemm(y, w2, out, h, wd, 1, True)
-            _conv_wgrad(dy, y, dw, 1, 1, 1, 0)
+        def run(name):
+            if name == "apply":
+                C.bn_forward_partials(part, part.shape[2], x, None, y, bn.weight, bn.bias, rm, rv, mean, invstd, scale,
+                                      shift, c, eps, mom, True, None)
+                _conv1x1_gemm(y, w2, out, h, wd, 1, True)
+                _conv_wgrad(dy, y, dw, 1, 1, 1, 0)
+            else:
+                C.bn_finalize_partials(part, part.shape[2], n * h * wd, bn.weight, bn.bias, rm, rv, mean, invstd,
+                                       scale, shift, c, eps, mom)
+                _conv_pro_fwd(x, w, 1, 0, scale, shift)
+                _conv_wgrad_pro(dy, x, dw, 1, 1, 1, 0, scale, shift)
 
-        def pro():
-            C.bn_finalize_partials(part, part.shape[2], n * h * wd, bn.weight, bn.bias, rm, rv, mean, invstd, scale,
-                                   shift, c, eps, mom)
-            _conv_pro_fwd(x, w, 1, 0, scale, shift)
-            _conv_wgrad_pro(dy, x, dw, 1, 1, 1, 0, scale, shift)
-
-        got = TUNER.pick(key, {"apply": apply, "pro": pro})
+        got = TUNER.pick(key, ["apply", "pro"], run)
     return got == "pro"
 
 
@@ -940,6 +803,15 @@ class ResidualLink:
         return g
 
 
+def _g2_ok(*ts) -> bool:
+    return all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in ts)
+
+
+def _g2_linear_ok(M: int, N: int, K: int, *ts) -> bool:
+    """Are the gemm2 tiles candidates for an [M, K] x [N, K]^T Linear GEMM over the operands ``ts``?"""
+    return _GEMM2 and N % 64 == 0 and K % 64 == 0 and M >= 1024 and _g2_ok(*ts)
+
+
 def _linear_fwd(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
                 res: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x2 w^T (+ bias) (+ res) (bf16 [M, K] x [N, K] (+ bf16 [M, N]) -> [M, N]): per shape the
@@ -956,8 +828,12 @@ def _linear_fwd(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] 
         return torch.ops.aten.addmm.dtype(res, x2, w.t(), torch.float32)
     y = torch.empty((M, N), dtype=torch.bfloat16, device=x2.device)
 
-    def blas():
-        if res is not None:
+    def run(name):
+        if name != "blas":
+            bm, bn, ns = _g2_parse(name)
+            native().gemm2_conv(x2, w, y, None, res, None, 1, 1, 1, 1, 1, 0, bm, bn, stages=ns,
+                                bias=None if bias is None else bias.detach())
+        elif res is not None:
             torch.addmm(res, x2, w.t(), out=y)
             if bias is not None:
                 y.add_(bf16_weight(bias))
@@ -966,21 +842,12 @@ def _linear_fwd(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] 
         else:
             torch.addmm(bf16_weight(bias), x2, w.t(), out=y)
 
-    if not (_GEMM2 and N % 64 == 0 and K % 64 == 0 and M >= 1024 and x2.is_contiguous() and w.is_contiguous()
-            and x2.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0
+    name = "blas"
+    if (_g2_linear_ok(M, N, K, x2, w, y)
             and (bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N))
-            and (res is None or (res.dtype == torch.bfloat16 and res.is_contiguous() and res.data_ptr() % 16 == 0))):
-        blas()
-        return y
-    C = native()
-    cands = {"blas": blas}
-    b = None if bias is None else bias.detach()
-    for name in _g2_names(N):
-        bm, bn, ns = _g2_parse(name)
-        cands[name] = (lambda bm=bm, bn=bn, ns=ns:
-                       C.gemm2_conv(x2, w, y, None, res, None, 1, 1, 1, 1, 1, 0, bm, bn, stages=ns, bias=b))
-    pick = TUNER.pick(("lfwd", M, N, K, bias is not None, res is not None), cands)
-    cands[pick]()
+            and (res is None or (res.dtype == torch.bfloat16 and _g2_ok(res)))):
+        name = TUNER.pick(("lfwd", M, N, K, bias is not None, res is not None), ["blas"] + _g2_names(N), run)
+    run(name)
     return y
 
 
@@ -997,29 +864,17 @@ def _linear_wgrad(dy2: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
     K = x2.shape[1]
     dw = torch.empty((N, K), dtype=torch.float32, device=dy2.device)
 
-    def mm():
-        torch.ops.aten.mm.dtype_out(dy2.t(), x2, torch.float32, out=dw)
+    def run(name):
+        if name == "mm":
+            torch.ops.aten.mm.dtype_out(dy2.t(), x2, torch.float32, out=dw)
+        else:
+            native().gemm2_wgrad(dy2, x2, dw, 1, 1, 1, 0, 1, 1, *_wgrad_parse(name))
 
-    if not (_GEMM2 and N % 64 == 0 and K % 64 == 0 and M >= 1024 and dy2.is_contiguous() and x2.is_contiguous()
-            and dy2.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0):
-        mm()
-        return dw
-    C = native()
-    cands = {"mm": mm}
-    ok = {0: True, 1: N % 256 == 0 and K % 128 == 0, 2: N % 256 == 0 and K % 256 == 0,
-          3: N % 128 == 0 and K % 256 == 0, 4: N % 256 == 0 and K % 128 == 0}
-    for cfg in (0, 1, 2, 3, 4):
-        if ok[cfg]:
-            for ns in ((2, 3) if cfg != 2 else (2, 4)):
-                cands[f"w3_{cfg}" + ("" if ns == 2 else f"s{ns}")] = (
-                    lambda cfg=cfg, ns=ns: C.gemm2_wgrad(dy2, x2, dw, 1, 1, 1, 0, 1, 1, cfg, ns))
-    name = TUNER.pick(("lwgrad", M, N, K), cands)
-    cands[name]()
+    name = "mm"
+    if _g2_linear_ok(M, N, K, dy2, x2):
+        name = TUNER.pick(("lwgrad", M, N, K), ["mm"] + _wgrad_names(N, K, 1, "linear"), run)
+    run(name)
     return dw
-
-
-def _g2_ok(*ts) -> bool:
-    return all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in ts)
 
 
 def _gelu_linear_fwd(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]):
@@ -1031,26 +886,23 @@ def _gelu_linear_fwd(x2: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Ten
     pre = torch.empty((M, N), dtype=torch.bfloat16, device=x2.device)
     post = torch.empty_like(pre)
 
-    def blas():
+    def run(name):
+        if name != "blas":
+            bm, bn, ns = _g2_parse(name)
+            native().gemm2_conv(x2, w, post, None, None, None, 1, 1, 1, 1, 1, 0, bm, bn, stages=ns,
+                                bias=None if bias is None else bias.detach(), gelu_pre=pre, gelu=1)
+            return
         if bias is None:
             torch.mm(x2, w.t(), out=pre)
         else:
             torch.addmm(bf16_weight(bias), x2, w.t(), out=pre)
         torch._C._nn.gelu(pre, out=post)
 
-    if not (_GEMM2 and N % 64 == 0 and K % 64 == 0 and M >= 1024 and _g2_ok(x2, w)
+    name = "blas"
+    if (_g2_linear_ok(M, N, K, x2, w)
             and (bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N))):
-        blas()
-        return post, pre
-    C = native()
-    b = None if bias is None else bias.detach()
-    cands = {"blas": blas}
-    for name in _g2_names(N):
-        bm, bn, ns = _g2_parse(name)
-        cands[name] = (lambda bm=bm, bn=bn, ns=ns:
-                       C.gemm2_conv(x2, w, post, None, None, None, 1, 1, 1, 1, 1, 0, bm, bn, stages=ns, bias=b,
-                                    gelu_pre=pre, gelu=1))
-    cands[TUNER.pick(("gelu_fwd", M, N, K, bias is not None), cands)]()
+        name = TUNER.pick(("gelu_fwd", M, N, K, bias is not None), ["blas"] + _g2_names(N), run)
+    run(name)
     return post, pre
 
 
@@ -1064,18 +916,17 @@ def _gelu_dgrad(dy2: torch.Tensor, w: torch.Tensor, pre: torch.Tensor, wt=None, 
     M, N = dy2.shape
     K = w.shape[1]
 
-    def blas():
-        out = torch.ops.aten.gelu_backward(torch.mm(dy2, w), pre)
-        if bias_grad:
-            stash_colsum(out, colsum_f32(out))
-        return out
+    g2 = wt is not None and _g2_linear_ok(M, N, K, dy2, wt, pre)
+    out = torch.empty((M, K), dtype=torch.bfloat16, device=dy2.device) if g2 else None
 
-    if not (_GEMM2 and wt is not None and N % 64 == 0 and K % 64 == 0 and M >= 1024 and _g2_ok(dy2, wt, pre)):
-        return blas()
-    C = native()
-    out = torch.empty((M, K), dtype=torch.bfloat16, device=dy2.device)
-
-    def g2(bm, bn, ns):
+    def run(name):
+        if name == "blas":
+            o = torch.ops.aten.gelu_backward(torch.mm(dy2, w), pre)
+            if bias_grad:
+                stash_colsum(o, colsum_f32(o))
+            return o
+        C = native()
+        bm, bn, ns = _g2_parse(name)
         part = None
         if bias_grad:
             part = torch.empty((C.gemm2_mtiles(M, K, N, bm), K), dtype=torch.float32, device=dy2.device)
@@ -1086,11 +937,7 @@ def _gelu_dgrad(dy2: torch.Tensor, w: torch.Tensor, pre: torch.Tensor, wt=None, 
             stash_colsum(out, db)
         return out
 
-    cands = {"blas": blas}
-    for name in _g2_names(K):
-        bm, bn, ns = _g2_parse(name)
-        cands[name] = (lambda bm=bm, bn=bn, ns=ns: g2(bm, bn, ns))
-    return cands[TUNER.pick(("gelu_dgrad", M, N, K, bias_grad), cands)]()
+    return run(TUNER.pick(("gelu_dgrad", M, N, K, bias_grad), ["blas"] + _g2_names(K), run) if g2 else "blas")
 
 
 def _dgrad(dy2: torch.Tensor, w_master: torch.Tensor, add: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1101,26 +948,19 @@ def _dgrad(dy2: torch.Tensor, w_master: torch.Tensor, add: Optional[torch.Tensor
     w = bf16_weight(w_master, idle=False)
     M, N = dy2.shape
     K = w.shape[1]
-
-    def blas():
-        return torch.mm(dy2, w) if add is None else torch.addmm(add, dy2, w)
-
     wt = transposed_weight(w_master)
-    if not (_GEMM2 and wt is not None and add is not None and N % 64 == 0 and K % 64 == 0 and M >= 1024
-            and add.dtype == torch.bfloat16 and tuple(add.shape) == (M, K) and _g2_ok(dy2, wt, add)):
-        return blas()
-    C = native()
-    out = torch.empty((M, K), dtype=torch.bfloat16, device=dy2.device)
+    g2 = (wt is not None and add is not None and add.dtype == torch.bfloat16 and tuple(add.shape) == (M, K)
+          and _g2_linear_ok(M, N, K, dy2, wt, add))
+    out = torch.empty((M, K), dtype=torch.bfloat16, device=dy2.device) if g2 else None
 
-    def g2(bm, bn, ns):
-        C.gemm2_conv(dy2, wt, out, None, add, None, 1, 1, 1, 1, 1, 0, bm, bn, stages=ns)
+    def run(name):
+        if name == "blas":
+            return torch.mm(dy2, w) if add is None else torch.addmm(add, dy2, w)
+        bm, bn, ns = _g2_parse(name)
+        native().gemm2_conv(dy2, wt, out, None, add, None, 1, 1, 1, 1, 1, 0, bm, bn, stages=ns)
         return out
 
-    cands = {"blas": blas}
-    for name in _g2_names(K):
-        bm, bn, ns = _g2_parse(name)
-        cands[name] = (lambda bm=bm, bn=bn, ns=ns: g2(bm, bn, ns))
-    return cands[TUNER.pick(("dgrad_add", M, N, K), cands)]()
+    return run(TUNER.pick(("dgrad_add", M, N, K), ["blas"] + _g2_names(K), run) if g2 else "blas")
 
 
 class _GeluMLP(torch.autograd.Function):

@@ -474,3 +474,45 @@ def test_gemm2_wgrad_fewer_slabs(cfg, cin, cout, k, h, stride):
     C().gemm2_wgrad(dy, x, d2, k, k, stride, pad, h, h, cfg, 2, sdiv=2)
     torch.cuda.synchronize()
     torch.testing.assert_close(d2, d1, rtol=1e-5, atol=1e-4)
+
+
+# candidate name -> (cfg, stages) of the gemm2_wgrad launch it stands for
+W3_LAUNCH = {"w3_0": (0, 2), "w3_0s3": (0, 3), "w3_0s4": (0, 4), "w3_1": (1, 2), "w3_1s3": (1, 3), "w3_2": (2, 2),
+             "w3_2s4": (2, 4), "w3_3": (3, 2), "w3_3s3": (3, 3), "w3_4": (4, 2), "w3_4s3": (4, 3), "w3_5": (5, 2),
+             "w3_5s3": (5, 3), "w3_6": (6, 2), "w3_6s3": (6, 3)}
+
+
+@pytest.mark.parametrize("cin,cout,k,cfgs", [(64, 64, 3, {0, 5, 6}), (256, 256, 1, {0, 1, 2, 3, 4})])
+def test_conv_wgrad_launches_the_recorded_name(cin, cout, k, cfgs):
+    """_conv_wgrad with a recorded pick launches exactly that candidate: for every name it offers,
+    dw is bit-identical to the direct call of the kernel, configuration and stage count the name
+    stands for (the first core for 'w2')."""
+    from hipps.ops import nn as hnn
+
+    n, h, pad = 2, 8, k // 2
+    x, dy = _x(n, cin, h, 91), _x(n, cout, h, 92)
+    names = ["w2"] + hnn._wgrad_names(cout, cin, k * k, "conv")
+    assert {W3_LAUNCH[nm][0] for nm in names[1:]} == cfgs
+    key = ("wgrad", tuple(x.shape), cout, k, k, 1, pad)
+
+    def dws():
+        if k == 1:
+            return torch.full((cout, cin), 9.0, device=DEV), torch.full((cout, cin), 7.0, device=DEV)
+        return (torch.full((cout, cin, k, k), v, device=DEV).contiguous(memory_format=CL) for v in (9.0, 7.0))
+
+    try:
+        for name in names:
+            got, ref = dws()
+            hnn.TUNER.cache[key] = name
+            hnn._conv_wgrad(dy, x, got, k, k, 1, pad)
+            if name != "w2":
+                C().gemm2_wgrad(dy, x, ref, k, k, 1, pad, h, h, *W3_LAUNCH[name])
+            elif k == 1:
+                C().conv1x1_wgrad(dy, x, ref, h, h, 1)
+            else:
+                C().conv_wgrad(dy, x, ref, k, k, 1, pad)
+            torch.cuda.synchronize()
+            assert torch.equal(got, ref), name
+            assert hnn.TUNER.cache[key] == name
+    finally:
+        hnn.TUNER.cache.pop(key, None)

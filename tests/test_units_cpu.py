@@ -313,4 +313,4 @@ def test_tuner_picks_round_trip(tmp_path):
     t.save(f)
     u = _Tuner()
     assert u.load(f) == 2 and u.cache == t.cache
-    assert u.pick(("lfwd", 1024, 768, 768, True, False), {"x": None, "y": None}) == "g2_256x256"
+    assert u.pick(("lfwd", 1024, 768, 768, True, False), ["blas", "g2_256x256"], None) == "g2_256x256"

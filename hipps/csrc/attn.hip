@@ -491,7 +491,11 @@ __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
     }
   }
   if (key >= a.Sk) return;
-  const bool kok = key < kv_end;  // padded keys: zero gradient
+  // padded keys: zero gradient.  A select, not a multiply by 0: the wave's kf / vf hold the padded
+  // keys' own K / V rows, which may be anything (Inf / NaN after torch.empty), and so do the
+  // accumulator columns of those keys -- only those, a column depends on no other key
+  const bool kok = key < kv_end;
+  auto keep = [kok](float x) { return kok ? x : 0.f; };
   const float sc = a.scale;
   if (a.gsplit == 1) {
     const int64_t off = b * a.gkb + (int64_t)key * a.gks + hk * a.gkh;
@@ -500,11 +504,10 @@ __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int d = 32 * db + 8 * g + 4 * h;
-        const float z = kok ? 1.f : 0.f;
-        store4(a.dk + off + d, dka[db][4 * g] * sc * z, dka[db][4 * g + 1] * sc * z, dka[db][4 * g + 2] * sc * z,
-               dka[db][4 * g + 3] * sc * z);
-        store4(a.dv + off + d, dva[db][4 * g] * z, dva[db][4 * g + 1] * z, dva[db][4 * g + 2] * z,
-               dva[db][4 * g + 3] * z);
+        store4(a.dk + off + d, keep(dka[db][4 * g] * sc), keep(dka[db][4 * g + 1] * sc),
+               keep(dka[db][4 * g + 2] * sc), keep(dka[db][4 * g + 3] * sc));
+        store4(a.dv + off + d, keep(dva[db][4 * g]), keep(dva[db][4 * g + 1]), keep(dva[db][4 * g + 2]),
+               keep(dva[db][4 * g + 3]));
       }
   } else {
     const int64_t n = (int64_t)a.B * a.Sk * a.Hkv * D;
@@ -515,11 +518,10 @@ __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int d = 32 * db + 8 * g + 4 * h;
-        const float z = kok ? 1.f : 0.f;
-        *reinterpret_cast<float4*>(pk + d) = make_float4(dka[db][4 * g] * sc * z, dka[db][4 * g + 1] * sc * z,
-                                                         dka[db][4 * g + 2] * sc * z, dka[db][4 * g + 3] * sc * z);
-        *reinterpret_cast<float4*>(pv + d) =
-            make_float4(dva[db][4 * g] * z, dva[db][4 * g + 1] * z, dva[db][4 * g + 2] * z, dva[db][4 * g + 3] * z);
+        *reinterpret_cast<float4*>(pk + d) = make_float4(keep(dka[db][4 * g] * sc), keep(dka[db][4 * g + 1] * sc),
+                                                         keep(dka[db][4 * g + 2] * sc), keep(dka[db][4 * g + 3] * sc));
+        *reinterpret_cast<float4*>(pv + d) = make_float4(keep(dva[db][4 * g]), keep(dva[db][4 * g + 1]),
+                                                         keep(dva[db][4 * g + 2]), keep(dva[db][4 * g + 3]));
       }
   }
 }

@@ -125,6 +125,11 @@ class Bert(nn.Module):
     def forward(self, ids, labels=None, kv_len=None):
         """``kv_len``: optional int32 [B] valid lengths of a right-padded batch (key padding mask)."""
         B, S = ids.shape
+        if (torch.is_tensor(kv_len) and kv_len.dim() == 1
+                and kv_len.dtype in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)):
+            # integer lengths of any width (torch.tensor([...]) is int64) are key lengths: the layers
+            # take only an int32 [B] tensor as such and read anything else as an SDPA attn_mask
+            kv_len = kv_len.to(device=ids.device, dtype=torch.int32)
         if hnn.bert_embed_ok(ids, self.word.weight, self.pos.weight, self.tok_type.weight):
             # one gather-add pass, deterministic table gradients (csrc/embed.hip); type ids all 0
             x = hnn.bert_embed(ids, self.word.weight, self.pos.weight, self.tok_type.weight)

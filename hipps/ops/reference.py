@@ -2,7 +2,8 @@
 
 Two roles:
   * the CPU backend (gloo plumbing tests, BASELINE config 1 "MLP sync PS on CPU");
-  * the numerics oracle the GPU kernel tests compare against (fp32 torch math).
+  * the numerics oracle the GPU kernel tests compare against (fp32 torch math; fp64 for
+    attention, with a mode that rounds to bf16 where csrc/attn.hip does).
 
 Semantics mirror the HIP kernels exactly (rank-ordered sums, reference SGD/Adam formulas from
 /root/reference/ps.py:197-261, 256-element int8 blocks, exact top-k with lowest-index tie
@@ -293,3 +294,73 @@ def thresh_encode(g, resid, tau, count, idx, val, workspace=None):
 def thresh_accumulate(count, idx, val, acc, gscale=1.0):
     k = min(int(count[0]), idx.numel())
     acc.index_add_(0, idx[:k].long(), val[:k].float() * gscale)
+
+
+# ---- attention (csrc/attn.hip) -------------------------------------------------------------
+def _bf16_round(t: torch.Tensor) -> torch.Tensor:
+    return t.to(torch.bfloat16).to(torch.float64)
+
+
+def attention(q, k, v, dout, causal=False, kv_len=None, scale=None, emulate_bf16=False):
+    """fp64 oracle of csrc/attn.hip, forward and an explicit (no autograd) backward.
+
+    q / dout [B, Sq, Hq, D], k / v [B, Sk, Hkv, D] (GQA by repetition: query head h reads kv head
+    h // (Hq / Hkv)); ``causal`` masks key > query row, ``kv_len`` [B] masks key >= kv_len[b]
+    (values above Sk behave as Sk).  Returns fp64 (o [B, Sq, Hq, D], lse [B, Hq, Sq], dq, dk, dv).
+    A row with every key masked has o = 0, lse = +inf and contributes no gradient.
+
+    ``emulate_bf16`` rounds to bf16 where the kernels do and nowhere else: exp(s - rowmax) before
+    P V (the row sum stays unrounded); exp(s - lse) before P^T dO; dS = P (dP - delta) before the
+    dQ and dK products; delta from the rounded o; o / dq / dk / dv themselves (lse to fp32).  Its
+    distance from the unrounded mode is the error a correct bf16 implementation of this algorithm
+    has on the given inputs."""
+    B, Sq, Hq, D = q.shape
+    Sk, Hkv = k.shape[1], k.shape[2]
+    G = Hq // Hkv
+    sc = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+    rnd = _bf16_round if emulate_bf16 else (lambda t: t)
+    qd, dod = (t.to(torch.float64).transpose(1, 2) for t in (q, dout))                    # [B, Hq, Sq, D]
+    kd, vd = (t.to(torch.float64).transpose(1, 2).repeat_interleave(G, 1) for t in (k, v))  # [B, Hq, Sk, D]
+    keys = torch.arange(Sk, device=q.device)
+    mask = torch.ones(B, 1, Sq, Sk, dtype=torch.bool, device=q.device)
+    if causal:
+        mask = mask & (keys[None, :] <= torch.arange(Sq, device=q.device)[:, None])
+    if kv_len is not None:
+        kl = torch.as_tensor(kv_len, device=q.device).view(B, 1, 1, 1)
+        mask = mask & (keys < kl)
+    mask = mask.expand(B, Hq, Sq, Sk)
+    s = (qd @ kd.transpose(-1, -2)) * sc
+    live = mask.any(-1, keepdim=True)
+    m = torch.where(live, s.masked_fill(~mask, -math.inf).amax(-1, keepdim=True), torch.zeros_like(s[..., :1]))
+    e = torch.where(mask, torch.exp(s - m), torch.zeros_like(s))
+    l = e.sum(-1, keepdim=True)
+    o = torch.where(live, (rnd(e) @ vd) / l.clamp_min(1e-300), torch.zeros_like(qd))
+    lse = torch.where(live, m + torch.log(l.clamp_min(1e-300)), torch.full_like(m, math.inf))
+    o = rnd(o)
+    if emulate_bf16:
+        lse = lse.float().to(torch.float64)
+    # backward: the kernels recompute P from the stored lse
+    p = torch.where(mask, torch.exp(s - lse), torch.zeros_like(s))
+    delta = (dod * o).sum(-1, keepdim=True)
+    ds = p * (dod @ vd.transpose(-1, -2) - delta)
+    # a one-key softmax is constant: dS is exactly zero there, not the rounding residue of dP - delta
+    ds = torch.where(mask.sum(-1, keepdim=True) == 1, torch.zeros_like(ds), ds)
+    ds = rnd(ds)
+    dq = (ds @ kd) * sc
+    dk = (ds.transpose(-1, -2) @ qd) * sc
+    dv = rnd(p).transpose(-1, -2) @ dod
+    dk, dv = (t.view(B, Hkv, G, Sk, D).sum(2) for t in (dk, dv))
+    return (o.transpose(1, 2), lse.squeeze(-1), rnd(dq).transpose(1, 2), rnd(dk).transpose(1, 2),
+            rnd(dv).transpose(1, 2))
+
+
+def attention_row_error(got: torch.Tensor, want: torch.Tensor) -> float:
+    """Largest per-row error of a [B, S, H, D] attention tensor, relative to the typical row:
+    max_row ||got - want||_2 / RMS_row ||want||_2 with the RMS over the rows where ``want`` is not
+    zero.  One wrong row shows at full size however many rows there are; rows whose own norm is
+    tiny from cancellation do not inflate it.  Needs a non-zero ``want``."""
+    g, w = got.to(torch.float64), want.to(torch.float64).to(got.device)
+    norms = w.norm(dim=-1)
+    nz = norms[norms > 0]
+    assert nz.numel() > 0, "attention_row_error: the reference is identically zero"
+    return ((g - w).norm(dim=-1).max() / nz.pow(2).mean().sqrt()).item()

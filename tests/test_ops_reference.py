@@ -186,3 +186,111 @@ def test_threshold_codec_variable_size_and_ef():
     v2 = lay2.views(torch.zeros(lay2.nbytes, dtype=torch.uint8))
     c2.encode_into(x, v2, c2.init_state(7, "cpu"))
     assert int(v2["count"][0]) == 2 and v2["idx"].tolist() == [0, 1]
+
+
+# ---- attention oracle (reference.attention) --------------------------------------------------
+def _attn_inputs(B, Sq, Sk, Hq, Hkv, D, seed):
+    """The sharp inputs of tests/test_attn_edges_gpu.py: bf16 randn with q scaled by 4, so the
+    scores have standard deviation ~4 and a few keys dominate each row."""
+    g = torch.Generator().manual_seed(seed)
+    q = (torch.randn(B, Sq, Hq, D, generator=g) * 4).to(torch.bfloat16)
+    k, v = (torch.randn(B, Sk, Hkv, D, generator=g).to(torch.bfloat16) for _ in range(2))
+    dout = torch.randn(B, Sq, Hq, D, generator=g).to(torch.bfloat16)
+    return q, k, v, dout
+
+
+def _attn_autograd(q, k, v, dout, causal, kv_len, scale):
+    qd, kd, vd = (t.double().requires_grad_(True) for t in (q, k, v))
+    G = q.shape[2] // k.shape[2]
+    s = (qd.transpose(1, 2) @ kd.transpose(1, 2).repeat_interleave(G, 1).transpose(-1, -2)) * scale
+    Sq, Sk = s.shape[-2:]
+    bias = torch.zeros(q.shape[0], 1, Sq, Sk, dtype=torch.float64)
+    if causal:
+        bias = bias.masked_fill(~torch.ones(Sq, Sk, dtype=torch.bool).tril(), -math.inf)
+    if kv_len is not None:
+        bias = bias.masked_fill((torch.arange(Sk)[None, :] >= torch.tensor(kv_len)[:, None])[:, None, None, :],
+                                -math.inf)
+    s = s + bias
+    o = (torch.softmax(s, -1) @ vd.transpose(1, 2).repeat_interleave(G, 1)).transpose(1, 2)
+    lse = torch.logsumexp(s, -1)
+    o.backward(dout.double())
+    return o.detach(), lse.detach(), qd.grad, kd.grad, vd.grad
+
+
+ATTN_ORACLE_CASES = [
+    # B, Sq, Sk, Hq, Hkv, D, causal, kv_len, scale
+    (2, 17, 17, 2, 2, 64, False, None, None),
+    (2, 70, 70, 2, 2, 64, True, None, 0.37),
+    (3, 40, 40, 2, 2, 32, False, [1, 33, 47], None),   # one key, a partial row, above Sk
+    (2, 40, 40, 2, 2, 32, True, [9, 40], None),
+    (2, 33, 33, 6, 2, 16, True, None, None),            # GQA
+    (1, 33, 33, 3, 1, 16, False, [20], 0.2),
+    (2, 50, 21, 4, 2, 32, False, None, None),           # Sq != Sk
+    (2, 5, 61, 2, 1, 32, False, [61, 7], None),
+]
+
+
+@pytest.mark.parametrize("B,Sq,Sk,Hq,Hkv,D,causal,kv_len,scale", ATTN_ORACLE_CASES)
+def test_attention_oracle_matches_fp64_autograd(B, Sq, Sk, Hq, Hkv, D, causal, kv_len, scale):
+    q, k, v, dout = _attn_inputs(B, Sq, Sk, Hq, Hkv, D, seed=Sq + Sk + Hq)
+    sc = scale if scale is not None else D ** -0.5
+    got = ref.attention(q, k, v, dout, causal, None if kv_len is None else torch.tensor(kv_len), scale)
+    want = _attn_autograd(q, k, v, dout, causal, kv_len, sc)
+    for g, w, name in zip(got, want, ("o", "lse", "dq", "dk", "dv")):
+        assert g.dtype == torch.float64 and g.shape == w.shape, name
+        torch.testing.assert_close(g, w, rtol=1e-10, atol=1e-10, msg=lambda m, n=name: "%s: %s" % (n, m))
+
+
+@pytest.mark.parametrize("emulate", [False, True])
+def test_attention_oracle_fully_masked_rows(emulate):
+    """kv_len = 0: o = 0, lse = +inf, no gradient from or to that batch row; the others are what
+    they are without it."""
+    q, k, v, dout = _attn_inputs(3, 9, 12, 4, 2, 16, seed=3)
+    o, lse, dq, dk, dv = ref.attention(q, k, v, dout, False, torch.tensor([5, 0, 12]), None, emulate)
+    for t in (o, dq, dk, dv):
+        assert torch.isfinite(t).all() and torch.count_nonzero(t[1]) == 0
+    assert (lse[1] == math.inf).all() and torch.isfinite(lse[[0, 2]]).all()
+    assert torch.count_nonzero(dk[0, 5:]) == 0 and torch.count_nonzero(dv[0, 5:]) == 0
+    rest = ref.attention(q[[0, 2]], k[[0, 2]], v[[0, 2]], dout[[0, 2]], False, torch.tensor([5, 12]), None, emulate)
+    for t, r in zip((o, lse, dq, dk, dv), rest):
+        assert torch.equal(t[[0, 2]], r)
+
+
+def test_attention_oracle_one_key_rows_have_exactly_zero_score_gradient():
+    """A softmax over one key is constant: dq and dk are exactly zero, dv is the sum of dout."""
+    q, k, v, dout = _attn_inputs(2, 7, 1, 2, 1, 16, seed=4)
+    for emulate in (False, True):
+        o, lse, dq, dk, dv = ref.attention(q, k, v, dout, False, None, None, emulate)
+        assert torch.equal(o, v.double().expand(2, 7, 2, 16))
+        assert torch.count_nonzero(dq) == 0 and torch.count_nonzero(dk) == 0
+        if not emulate:
+            torch.testing.assert_close(dv, dout.double().sum((1, 2), keepdim=True), rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize("B,Sq,Sk,Hq,Hkv,D,causal,kv_len,scale", [
+    (2, 17, 17, 2, 2, 64, True, None, None),
+    (2, 200, 200, 2, 2, 64, False, None, None),
+    (1, 130, 75, 4, 2, 128, False, [60], 0.37),
+])
+def test_attention_oracle_emulated_error_is_a_yardstick(B, Sq, Sk, Hq, Hkv, D, causal, kv_len, scale):
+    """The bf16-emulating mode differs from the exact one (it rounds) by a few per cent at the
+    most in the per-row metric (it rounds nothing else), and its outputs are bf16 values."""
+    q, k, v, dout = _attn_inputs(B, Sq, Sk, Hq, Hkv, D, seed=Sq)
+    kl = None if kv_len is None else torch.tensor(kv_len)
+    exact = ref.attention(q, k, v, dout, causal, kl, scale)
+    emu = ref.attention(q, k, v, dout, causal, kl, scale, emulate_bf16=True)
+    for e, x, name in zip(emu, exact, ("o", "lse", "dq", "dk", "dv")):
+        if name == "lse":
+            torch.testing.assert_close(e, x, rtol=1e-6, atol=1e-6)
+            continue
+        assert torch.equal(e, e.to(torch.bfloat16).double()), name
+        err = ref.attention_row_error(e, x)
+        assert 0.0 < err < 0.05, (name, err)
+
+
+def test_attention_row_error_sees_one_wrong_row():
+    want = torch.randn(2, 300, 4, 64, dtype=torch.float64)
+    got = want.clone()
+    got[1, 177, 2] = 0.0
+    assert 0.8 < ref.attention_row_error(got, want) < 1.3
+    assert ref.attention_row_error(want, want) == 0.0

@@ -27,8 +27,8 @@ from hipps import codecs  # noqa: E402
 # threshold:0.02:0.05 saturates on this data (x ~ 0.01 randn with error feedback: the message is at its
 # 5 % cap from the second call on and most of the residual exceeds tau, profiles/codec/r5/ab_topk.txt);
 # threshold:0.1:0.05 stays below its cap (~1 % sent per call)
-SPECS = ["fp32", "bf16", "int8", "int8_sr", "topk:0.01", "topk_bf16:0.01", "topk_int8:0.01", "threshold:0.02:0.05",
-         "threshold:0.1:0.05"]
+SPECS = ["fp32", "bf16", "int8", "int8_sr", "mx4", "topk:0.01", "topk_bf16:0.01", "topk_int8:0.01",
+         "threshold:0.02:0.05", "threshold:0.1:0.05"]
 
 
 _FLUSH = None
@@ -76,14 +76,14 @@ def timed(fn, dev, iters, cold=True):
 
 def _enc_bytes(spec, n, wire, ef):
     """Minimum HBM traffic of one encode as the kernels are built (reads + writes), for the
-    effective-bandwidth column: dense casts read x and write the wire; int8 with error feedback
-    also reads and rewrites the residual; top-k and threshold make one full pass (fold: x, r read +
-    r written) plus passes over a candidate list of a few % of the bucket (not counted)."""
+    effective-bandwidth column: dense casts read x and write the wire; int8 and mx4 with error
+    feedback also read and rewrite the residual; top-k and threshold make one full pass (fold: x, r
+    read + r written) plus passes over a candidate list of a few % of the bucket (not counted)."""
     f = 4 * n
     name = spec.split(":")[0]
     if name in ("fp32", "bf16"):
         return f + wire
-    if name.startswith("int8"):
+    if name.startswith("int8") or name == "mx4":
         return f + wire + (2 * f if ef else 0)
     if name.startswith("topk") or name.startswith("thresh"):
         return (3 * f if ef else f) + wire

@@ -190,6 +190,29 @@ class Int8(Codec):
         ops.q8_aggregate([m["q"] for m in msgs], [m["scales"] for m in msgs], acc, gscale, accumulate, acquire)
 
 
+class MX4(Codec):
+    """OCP MXFP4: 4-bit e2m1 codes with one E8M0 power-of-two scale byte per 32 elements
+    (0.53125 B/elem), round-to-nearest, error feedback by default."""
+
+    name = "mx4"
+
+    def __init__(self, error_feedback: bool = True):
+        super().__init__()
+        self.error_feedback = error_feedback
+
+    def layout(self, n):
+        return WireLayout([("scales", torch.uint8, (n + ops.MXBLOCK - 1) // ops.MXBLOCK), ("q", torch.uint8, (n + 1) // 2)])
+
+    def init_state(self, n, device):
+        return {"resid": torch.zeros(n, dtype=torch.float32, device=device)} if self.error_feedback else {}
+
+    def encode_into(self, x, views, state):
+        ops.mx4_encode(x, state.get("resid"), views["q"], views["scales"])
+
+    def accumulate(self, msgs, acc, gscale=1.0, accumulate=False, acquire=False):
+        ops.mx4_aggregate([m["q"] for m in msgs], [m["scales"] for m in msgs], acc, gscale, accumulate, acquire)
+
+
 class TopK(Codec):
     """Exact magnitude top-k (k = ceil(ratio*n)), ascending int32 indices + f32/bf16 values."""
 
@@ -457,7 +480,7 @@ class ObjectCodec(Codec):
 
 
 def get_codec(spec) -> Codec:
-    """'fp32' | 'bf16' | 'int8' | 'int8_sr' | 'topk[:ratio]' | 'topk_bf16[:ratio]' | 'topk_int8[:ratio]' |
+    """'fp32' | 'bf16' | 'int8' | 'int8_sr' | 'mx4' (alias 'mxfp4') | 'topk[:ratio]' | 'topk_bf16[:ratio]' | 'topk_int8[:ratio]' |
     'threshold[:tau[:max_ratio]]' | Codec instance | any object with encode()/decode() (the
     reference's ``codings`` contract, wrapped in :class:`ObjectCodec`)."""
     if spec is None:
@@ -476,6 +499,8 @@ def get_codec(spec) -> Codec:
         return Int8(stochastic=False)
     if name in ("int8_sr", "qsgd_sr"):
         return Int8(stochastic=True)
+    if name in ("mx4", "mxfp4"):
+        return MX4()
     if name in ("threshold", "thresh"):
         tau, _, mr = arg.partition(":")
         return Threshold(tau=float(tau) if tau else 1e-3, max_ratio=float(mr) if mr else 0.05)
@@ -489,4 +514,4 @@ def get_codec(spec) -> Codec:
     raise ValueError(f"unknown codec {spec!r}")
 
 
-__all__ = ["Codec", "Identity", "Int8", "TopK", "TopKInt8", "Threshold", "ObjectCodec", "WireLayout", "get_codec"]
+__all__ = ["Codec", "Identity", "Int8", "MX4", "TopK", "TopKInt8", "Threshold", "ObjectCodec", "WireLayout", "get_codec"]

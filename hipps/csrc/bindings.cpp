@@ -22,6 +22,10 @@ void q8_encode(at::Tensor x, c10::optional<at::Tensor> resid, at::Tensor q, at::
                int64_t seed);
 void q8_aggregate(const std::vector<at::Tensor>& qs, const std::vector<at::Tensor>& ss, at::Tensor acc, double gscale,
                   bool accumulate, bool acquire);
+// mx4.hip
+void mx4_encode(at::Tensor x, c10::optional<at::Tensor> resid, at::Tensor q, at::Tensor scales);
+void mx4_aggregate(const std::vector<at::Tensor>& qs, const std::vector<at::Tensor>& ss, at::Tensor acc, double gscale,
+                   bool accumulate, bool acquire);
 // topk.hip
 void topk_encode(at::Tensor g, c10::optional<at::Tensor> resid, int64_t k, at::Tensor idx, at::Tensor val,
                  at::Tensor workspace);
@@ -193,6 +197,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("mask") = pybind11::none(), pybind11::arg("csteps") = pybind11::none());
   m.def("q8_encode", &hipps::q8_encode, "per-256-block absmax int8 quantization (+EF, +stochastic)");
   m.def("q8_aggregate", &hipps::q8_aggregate, "acc (+)= gscale * sum_w dequant(q_w, s_w)", py::arg("qs"), py::arg("ss"),
+        py::arg("acc"), py::arg("gscale"), py::arg("accumulate"), py::arg("acquire") = false);
+  m.def("mx4_encode", &hipps::mx4_encode, "MXFP4: e2m1 codes + one E8M0 scale byte per 32 elements (+EF)");
+  m.def("mx4_aggregate", &hipps::mx4_aggregate, "acc (+)= gscale * sum_w dequant(q_w, s_w)", py::arg("qs"), py::arg("ss"),
         py::arg("acc"), py::arg("gscale"), py::arg("accumulate"), py::arg("acquire") = false);
   m.def("topk_encode", &hipps::topk_encode, "exact top-k |g| (radix select) -> idx asc, val");
   m.def("topk_workspace_bytes", &hipps::topk_workspace_bytes, py::arg("n"), py::arg("k") = 0);

@@ -40,6 +40,8 @@ void adam_step(const std::vector<at::Tensor>& grads, double gscale, at::Tensor p
                bool amsgrad, bool torch_mode, c10::optional<at::Tensor> mask, c10::optional<at::Tensor> csteps);
 void q8_aggregate(const std::vector<at::Tensor>& qs, const std::vector<at::Tensor>& ss, at::Tensor acc, double gscale,
                   bool accumulate, bool acquire);
+void mx4_aggregate(const std::vector<at::Tensor>& qs, const std::vector<at::Tensor>& ss, at::Tensor acc, double gscale,
+                   bool accumulate, bool acquire);
 void topk_accumulate(at::Tensor idx, at::Tensor val, at::Tensor acc, double gscale, bool acquire);
 void topk_q8_accumulate(at::Tensor idx, at::Tensor q, at::Tensor scales, at::Tensor acc, double gscale,
                         bool acquire);
@@ -50,7 +52,7 @@ namespace rt {
 void emu_sweep(at::Tensor wr, at::Tensor rd, at::Tensor sink, int64_t stamp, int64_t blocks);
 
 // codec of a bucket's message (hipps/codecs): which fields, in which order
-enum Kind : int { kDense = 0, kQ8 = 1, kTopk = 2, kTopkQ8 = 3, kThresh = 4 };
+enum Kind : int { kDense = 0, kQ8 = 1, kTopk = 2, kTopkQ8 = 3, kThresh = 4, kMx4 = 5 };
 
 struct MsgField {
   int64_t off, numel;
@@ -466,13 +468,17 @@ class NativePS {
         aggregate(xs, acc, scale, true, acquire);
         break;
       }
-      case kQ8: {  // fields: q, scales
+      case kQ8:     // fields: q, scales
+      case kMx4: {  // the same two fields
         std::vector<at::Tensor> qs, ss;
         for (auto* m : msgs) {
           qs.push_back(V(m, 0));
           ss.push_back(V(m, 1));
         }
-        q8_aggregate(qs, ss, acc, scale, true, acquire);
+        if (b.kind == kMx4)
+          mx4_aggregate(qs, ss, acc, scale, true, acquire);
+        else
+          q8_aggregate(qs, ss, acc, scale, true, acquire);
         break;
       }
       case kTopk:  // idx, val

@@ -16,6 +16,7 @@ from ._native import available as native_available  # noqa: F401
 from ._native import native
 
 QBLOCK = ref.QBLOCK
+MXBLOCK = ref.MXBLOCK
 
 
 def _dev(t: torch.Tensor) -> bool:
@@ -92,6 +93,20 @@ def q8_aggregate(qs, ss, acc, gscale: float = 1.0, accumulate: bool = False, acq
     if _dev(acc):
         return native().q8_aggregate(list(qs), list(ss), acc, float(gscale), bool(accumulate), bool(acquire))
     return ref.q8_aggregate(qs, ss, acc, gscale, accumulate)
+
+
+def mx4_encode(x, resid, q, scales):
+    """MXFP4 message of x (+ resid): uint8 scales[ceil(n/32)], uint8 q[ceil(n/2)]; resid <- the
+    rounding error.  :func:`hipps.ops.reference.mx4_encode` defines the format."""
+    if _dev(x):
+        return native().mx4_encode(x, resid, q, scales)
+    return ref.mx4_encode(x, resid, q, scales)
+
+
+def mx4_aggregate(qs, ss, acc, gscale: float = 1.0, accumulate: bool = False, acquire: bool = False):
+    if _dev(acc):
+        return native().mx4_aggregate(list(qs), list(ss), acc, float(gscale), bool(accumulate), bool(acquire))
+    return ref.mx4_aggregate(qs, ss, acc, gscale, accumulate)
 
 
 def topk_workspace_bytes(n: int, k: int = 0) -> int:

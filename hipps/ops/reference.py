@@ -238,6 +238,72 @@ def q8_aggregate(qs, ss, acc, gscale=1.0, accumulate=False):
         acc.copy_(d)
 
 
+# ---- MXFP4 (OCP MX: e2m1 elements, one E8M0 scale byte per 32) ---------------------------------
+# This twin DEFINES the mx4 wire format; csrc/mx4.hip matches it bit for bit.
+MXBLOCK = 32
+MX4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def mx4_encode(x, resid, q, scales):
+    """scales[ceil(n/32)] (uint8, e + 127) and q[ceil(n/2)] (uint8, element 2j in the low nibble) of
+    v = x (+ resid); resid <- v - deq.  Per 32-block, a = max|v| (zeros pad the last block):
+    any non-finite element -> byte 255, codes 0, residual 0; a < 2^-100 -> byte 0, codes 0,
+    residual v; else the smallest e <= 125 with 6 * 2^e >= a and round-to-nearest codes, ties to
+    the even code.  The |v| bit patterns order like the magnitudes with Inf / NaN on top, so the
+    three cases and e are read from their integer maximum."""
+    v = _f32(x).clone()
+    if resid is not None:
+        v += resid
+    n = v.numel()
+    nb = (n + MXBLOCK - 1) // MXBLOCK
+    vb = torch.cat([v, v.new_zeros(nb * MXBLOCK - n)]).view(nb, MXBLOCK)
+    bits = vb.view(torch.int32)
+    amax = (bits & 0x7FFFFFFF).amax(dim=1)
+    nonfinite = amax >= 0x7F800000
+    tiny = amax < (27 << 23)  # 2^-100
+    normal = ~(nonfinite | tiny)
+    # a = m * 2^k, m in [1, 2): e = k - 2 if m <= 1.5 else k - 1, capped so 6 * 2^e stays finite
+    e = ((amax >> 23) - 127 - 2 + ((amax & 0x7FFFFF) > 0x400000).int()).clamp(max=125)
+    e = torch.where(normal, e, torch.zeros_like(e))
+    y = torch.ldexp(vb.abs(), -e[:, None])
+    mag = ((y > 0.25).int() + (y >= 0.75).int() + (y > 1.25).int() + (y >= 1.75).int() + (y > 2.5).int()
+           + (y >= 3.5).int() + (y > 5.0).int())
+    sign = (bits >> 31) & 1
+    code = torch.where(normal[:, None], (sign << 3) | mag, torch.zeros_like(mag))
+    grid = torch.tensor(MX4_GRID, dtype=torch.float32)
+    deq = torch.ldexp(torch.where(sign.bool(), -grid[mag], grid[mag]), e[:, None])  # exact
+    new = torch.where(normal[:, None], vb - deq, torch.where(tiny[:, None], vb, torch.zeros_like(vb)))
+    c = torch.cat([code.view(-1)[:n], code.new_zeros(n & 1)]).view(-1, 2)
+    q.copy_((c[:, 0] | (c[:, 1] << 4)).to(torch.uint8))
+    byte = torch.where(nonfinite, torch.full_like(e, 255), torch.where(tiny, torch.zeros_like(e), e + 127))
+    scales.copy_(byte.to(torch.uint8))
+    if resid is not None:
+        resid.copy_(new.view(-1)[:n])
+
+
+def mx4_dequant(q, scales, n):
+    """fp32[n] of one message: +-GRID[code & 7] * 2^(byte - 127); byte 255 -> NaN for the block."""
+    c = torch.stack([q & 15, q >> 4], dim=1).view(-1)[:n].long()
+    grid = torch.tensor(MX4_GRID, dtype=torch.float32)
+    val = torch.where((c & 8) != 0, -grid[c & 7], grid[c & 7])
+    b = scales.to(torch.int32).repeat_interleave(MXBLOCK)[:n]
+    d = torch.ldexp(val, b - 127)
+    return torch.where(b == 255, torch.full_like(d, float("nan")), d)
+
+
+def mx4_aggregate(qs, ss, acc, gscale=1.0, accumulate=False):
+    n = acc.numel()
+    g = torch.tensor(gscale, dtype=torch.float32)
+    if accumulate:  # each message added on its own (batch-invariant; csrc/mx4.hip k_mx4_aggregate)
+        for q, s in zip(qs, ss):
+            acc.add_(mx4_dequant(q, s, n) * g)
+        return
+    d = mx4_dequant(qs[0], ss[0], n)
+    for q, s in zip(qs[1:], ss[1:]):
+        d += mx4_dequant(q, s, n)
+    acc.copy_(d * g)
+
+
 def topk_select(x: torch.Tensor, k: int):
     """Exact top-k by |x| with lowest-index tie break; returns ascending indices."""
     key = x.float().abs()

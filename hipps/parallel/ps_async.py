@@ -1184,6 +1184,8 @@ class PSAsyncEngine(Engine):
             return 3, ("idx", "q", "scales")
         if t is cd.Threshold:
             return 4, ("count", "idx", "val")
+        if t is cd.MX4:
+            return 5, ("q", "scales")
         return None
 
     def _make_native(self, cfg, codec):

@@ -29,6 +29,12 @@
 //     S = Q K^T (accumulator initialised to -lse per query row, so p = exp2(c * acc)),
 //     dP = dO V^T (initialised to -delta), dV^T += dO^T P, dK^T += Q^T dS.
 //
+// Masks: causal and per-batch key lengths in the plain instantiations; the BND instantiations take
+// per-row ranges instead (packed documents, sliding windows, causal folded in): query i sees keys
+// [klo[i], khi[i]), key j is seen by queries [qlo[j], qhi[j]), all non-decreasing, so a workgroup
+// streams only the tiles its rows can see and a wave masks per element only at a range's edge
+// (RowRange below).  BND = false compiles to the plain kernels unchanged.
+//
 // LDS images: every tile is [rows][D] bf16 with the 16-byte chunk c of row r stored at chunk
 // c ^ f(r) -- one image serves the ds_read_b128 row reads (operand rows on the lanes) and the
 // ds_read_b64_tr_b16 transposed reads conflict-free (T10 'One image for row reads AND transposed
@@ -74,6 +80,13 @@ struct Args {
   int nblk;    // query blocks (forward / dQ) or key blocks (dK/dV) of QB rows
   int nqblk;   // query blocks (the rowstat tiles per (b, hq) are 2 * nqblk)
   int gsplit;  // dK/dV: slices of the GQA group (1 = write bf16 dK / dV directly)
+  // BND kernels (row-range masks: packed documents, sliding windows; Sq == Sk): int32 [B or 1, S],
+  // query i sees keys [klo[i], khi[i]), key j is seen by queries [qlo[j], qhi[j]); each array is
+  // non-decreasing along S (trusted, not checked: a violation masks wrongly, it never takes an
+  // address out of range).  The causal bound is folded into khi / qlo.
+  const int *klo, *khi, *qlo, *qhi;
+  int64_t bsb;  // their batch stride (0: one row for every batch)
+  int rev;      // forward / dQ: launch the query blocks last-first (the heaviest first under causal)
 };
 
 template <int D> __device__ __forceinline__ int swz(int row) {
@@ -179,21 +192,53 @@ __device__ __forceinline__ void store4(uint16_t* p, float a, float b, float c, f
   *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16x2(a, b), pack_bf16x2(c, d));
 }
 
+// Row ranges of a BND kernel for one lane.  "Rows" are the query rows of forward / dQ (ranges of
+// keys, streamed in key tiles) or the keys of dK/dV (ranges of queries, streamed in query tiles).
+// lo / hi non-decreasing => over any run of rows the smallest lo / hi is the first row's and the
+// largest the last row's.  Every row index is clamped to [0, S-1] and every tile index to
+// [0, ntiles]; the upper ends are clipped to ``end`` (kv_end, or Sq in dK/dV), so no content of
+// the arrays reaches an address.
+struct RowRange {
+  int t0, t1;    // the workgroup's tiles [t0, t1)
+  int wlo, whi;  // (wave-uniform) union of the wave's ranges: a tile outside it is skipped
+  int ilo, ihi;  // (wave-uniform) intersection of the wave's ranges: a tile inside it needs no mask
+  int lo, hi;    // the lane's own row
+};
+__device__ __forceinline__ RowRange row_range(const int* lo, const int* hi, int r0, int rw0, int row, int S, int end,
+                                              int ntiles) {
+  RowRange x;
+  const int rl = min(r0 + QB - 1, S - 1), wf = min(rw0, S - 1), wl = min(rw0 + 31, S - 1), rr = min(row, S - 1);
+  x.t0 = min(max(lo[min(r0, S - 1)], 0) / KT, ntiles);
+  x.t1 = min((max(min(hi[rl], end), 0) + KT - 1) / KT, ntiles);
+  x.wlo = lo[wf];
+  x.whi = min(hi[wl], end);
+  x.ilo = lo[wl];
+  x.ihi = min(hi[wf], end);
+  x.lo = lo[rr];
+  x.hi = min(hi[rr], end);
+  return x;
+}
+
 // ------------------------------------------------------------------------------------ forward
-template <int D, bool CAUSAL, int NS = 2>
+template <int D, bool CAUSAL, int NS = 2, bool BND = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_fwd(Args a) {
+  static_assert(!(BND && CAUSAL), "BND: the causal bound is folded into khi / qlo");
   constexpr int DK = D / 16, DB = D / 32, TILE = KT * 2 * D;
   __shared__ __attribute__((aligned(16))) char lds[NS][2 * TILE];
   const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int h = lane >> 5;
   const int nbh = a.B * a.Hq, bid = blockIdx.x;
-  const int qblk = CAUSAL ? a.nblk - 1 - bid / nbh : bid / nbh;  // causal: heaviest blocks first
+  const int qblk = (CAUSAL || (BND && a.rev)) ? a.nblk - 1 - bid / nbh : bid / nbh;  // causal: heaviest blocks first
   const int bh = bid % nbh, b = bh / a.Hq, hq = bh - b * a.Hq, hk = hq / (a.Hq / a.Hkv);
   const int q0 = qblk * QB, qw0 = q0 + 32 * w, qrow = qw0 + (lane & 31);
   int kv_end = a.Sk;
   if (a.kvlen != nullptr) kv_end = min(kv_end, a.kvlen[b]);
   const int kv_stop = CAUSAL ? min(kv_end, q0 + QB) : kv_end;
-  const int ntile = (kv_stop + KT - 1) / KT;
+  RowRange rg{};
+  if constexpr (BND)
+    rg = row_range(a.klo + b * a.bsb, a.khi + b * a.bsb, q0, qw0, qrow, a.Sq, kv_end, (a.Sk + KT - 1) / KT);
+  const int it0 = BND ? rg.t0 : 0;  // the block's key tiles are [it0, ntile)
+  const int ntile = BND ? rg.t1 : (kv_stop + KT - 1) / KT;
   const uint16_t* kb = a.k + b * a.ksb + hk * a.ksh;
   const uint16_t* vb = a.v + b * a.vsb + hk * a.vsh;
   const uint16_t* qp = a.q + b * a.qsb + hq * a.qsh + (int64_t)min(qrow, a.Sq - 1) * a.qss + 8 * h;
@@ -207,21 +252,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
   float m = -INFINITY, lsum = 0.f;
   const float c = a.scale * kLog2e;
-  for (int p = 0; p < NS - 1 && p < ntile; ++p) {
-    stage_tile<D>(lds[p], kb, a.kss, p * KT, kv_end, w, lane);
-    stage_tile<D>(lds[p] + TILE, vb, a.vss, p * KT, kv_end, w, lane);
+  for (int p = 0; p < NS - 1 && it0 + p < ntile; ++p) {
+    stage_tile<D>(lds[p], kb, a.kss, (it0 + p) * KT, kv_end, w, lane);
+    stage_tile<D>(lds[p] + TILE, vb, a.vss, (it0 + p) * KT, kv_end, w, lane);
   }
-  for (int it = 0; it < ntile; ++it) {
+  for (int it = it0; it < ntile; ++it) {
     wait_tile<NS>(it + 1 < ntile, 2 * tile_glds<D>());
     __syncthreads();  // tile it landed for every wave; the slot of tile it-1 is free
     if (it + NS - 1 < ntile) {
-      char* nb = lds[(it + NS - 1) % NS];
+      char* nb = lds[(it - it0 + NS - 1) % NS];
       stage_tile<D>(nb, kb, a.kss, (it + NS - 1) * KT, kv_end, w, lane);
       stage_tile<D>(nb + TILE, vb, a.vss, (it + NS - 1) * KT, kv_end, w, lane);
     }
     const int k0 = it * KT;
-    if (CAUSAL && k0 > qw0 + 31) continue;  // (wave-uniform) every key above this wave's rows
-    const char* Kt = lds[it % NS];
+    // (wave-uniform) every key above this wave's rows / outside every range of the wave
+    if (BND ? (k0 + KT <= rg.wlo || k0 >= rg.whi) : (CAUSAL && k0 > qw0 + 31)) continue;
+    const char* Kt = lds[(it - it0) % NS];
     const char* Vt = Kt + TILE;
     f32x16 s[2];
 #pragma unroll
@@ -231,13 +277,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 #pragma unroll
       for (int dk = 0; dk < DK; ++dk) s[kk] = MFMA32(row_frag<D>(Kt, 32 * kk, dk, lane), qf[dk], s[kk]);
     }
-    if (k0 + KT > kv_end || (CAUSAL && k0 + KT - 1 > qw0)) {
+    if (BND ? (k0 < rg.ilo || k0 + KT > rg.ihi) : (k0 + KT > kv_end || (CAUSAL && k0 + KT - 1 > qw0))) {
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = k0 + 32 * kk + crow(r, h);
-          if (key >= kv_end || (CAUSAL && key > qrow)) s[kk][r] = -INFINITY;
+          if (BND ? (key < rg.lo || key >= rg.hi) : (key >= kv_end || (CAUSAL && key > qrow))) s[kk][r] = -INFINITY;
         }
     }
     float mx = -INFINITY;
@@ -292,20 +338,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 // ------------------------------------------------------------------------------- backward: dQ
 // Also computes delta = rowsum(dO * O) and publishes the per-row constants the dK/dV kernel
 // initialises its accumulators with (rowstat), so no separate preprocess pass reads dO and O.
-template <int D, bool CAUSAL, int NS>
+template <int D, bool CAUSAL, int NS, bool BND = false>
 __device__ __forceinline__ void attn_dq_body(const Args& a) {
+  static_assert(!(BND && CAUSAL), "BND: the causal bound is folded into khi / qlo");
   constexpr int DK = D / 16, DB = D / 32, TILE = KT * 2 * D;
   __shared__ __attribute__((aligned(16))) char lds[NS][2 * TILE];
   const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int h = lane >> 5;
   const int nbh = a.B * a.Hq, bid = blockIdx.x;
-  const int qblk = CAUSAL ? a.nblk - 1 - bid / nbh : bid / nbh;
+  const int qblk = (CAUSAL || (BND && a.rev)) ? a.nblk - 1 - bid / nbh : bid / nbh;
   const int bh = bid % nbh, b = bh / a.Hq, hq = bh - b * a.Hq, hk = hq / (a.Hq / a.Hkv);
   const int q0 = qblk * QB, qw0 = q0 + 32 * w, qrow = qw0 + (lane & 31);
   int kv_end = a.Sk;
   if (a.kvlen != nullptr) kv_end = min(kv_end, a.kvlen[b]);
   const int kv_stop = CAUSAL ? min(kv_end, q0 + QB) : kv_end;
-  const int ntile = (kv_stop + KT - 1) / KT;
+  RowRange rg{};
+  if constexpr (BND)
+    rg = row_range(a.klo + b * a.bsb, a.khi + b * a.bsb, q0, qw0, qrow, a.Sq, kv_end, (a.Sk + KT - 1) / KT);
+  const int it0 = BND ? rg.t0 : 0;  // the block's key tiles are [it0, ntile)
+  const int ntile = BND ? rg.t1 : (kv_stop + KT - 1) / KT;
   const uint16_t* kb = a.k + b * a.ksb + hk * a.ksh;
   const uint16_t* vb = a.v + b * a.vsb + hk * a.vsh;
   const bool qok = qrow < a.Sq;
@@ -336,21 +387,21 @@ __device__ __forceinline__ void attn_dq_body(const Args& a) {
   for (int db = 0; db < DB; ++db)
 #pragma unroll
     for (int r = 0; r < 16; ++r) dq[db][r] = 0.f;
-  for (int p = 0; p < NS - 1 && p < ntile; ++p) {
-    stage_tile<D>(lds[p], kb, a.kss, p * KT, kv_end, w, lane);
-    stage_tile<D>(lds[p] + TILE, vb, a.vss, p * KT, kv_end, w, lane);
+  for (int p = 0; p < NS - 1 && it0 + p < ntile; ++p) {
+    stage_tile<D>(lds[p], kb, a.kss, (it0 + p) * KT, kv_end, w, lane);
+    stage_tile<D>(lds[p] + TILE, vb, a.vss, (it0 + p) * KT, kv_end, w, lane);
   }
-  for (int it = 0; it < ntile; ++it) {
+  for (int it = it0; it < ntile; ++it) {
     wait_tile<NS>(it + 1 < ntile, 2 * tile_glds<D>());
     __syncthreads();
     if (it + NS - 1 < ntile) {
-      char* nb = lds[(it + NS - 1) % NS];
+      char* nb = lds[(it - it0 + NS - 1) % NS];
       stage_tile<D>(nb, kb, a.kss, (it + NS - 1) * KT, kv_end, w, lane);
       stage_tile<D>(nb + TILE, vb, a.vss, (it + NS - 1) * KT, kv_end, w, lane);
     }
     const int k0 = it * KT;
-    if (CAUSAL && k0 > qw0 + 31) continue;
-    const char* Kt = lds[it % NS];
+    if (BND ? (k0 + KT <= rg.wlo || k0 >= rg.whi) : (CAUSAL && k0 > qw0 + 31)) continue;
+    const char* Kt = lds[(it - it0) % NS];
     const char* Vt = Kt + TILE;
     f32x16 s[2], dp[2];
 #pragma unroll
@@ -365,7 +416,7 @@ __device__ __forceinline__ void attn_dq_body(const Args& a) {
 #pragma unroll
       for (int dk = 0; dk < DK; ++dk) dp[kk] = MFMA32(row_frag<D>(Vt, 32 * kk, dk, lane), df[dk], dp[kk]);
     }
-    const bool msk = k0 + KT > kv_end || (CAUSAL && k0 + KT - 1 > qw0);
+    const bool msk = BND ? (k0 < rg.ilo || k0 + KT > rg.ihi) : (k0 + KT > kv_end || (CAUSAL && k0 + KT - 1 > qw0));
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
@@ -373,7 +424,7 @@ __device__ __forceinline__ void attn_dq_body(const Args& a) {
         float p = fast_exp2(fmaf(s[kk][r], c, -lse2));
         if (msk) {
           const int key = k0 + 32 * kk + crow(r, h);
-          if (key >= kv_end || (CAUSAL && key > qrow)) p = 0.f;
+          if (BND ? (key < rg.lo || key >= rg.hi) : (key >= kv_end || (CAUSAL && key > qrow))) p = 0.f;
         }
         s[kk][r] = p * dp[kk][r];  // dS^T
       }
@@ -399,8 +450,9 @@ __device__ __forceinline__ void attn_dq_body(const Args& a) {
 }
 
 // ---------------------------------------------------------------------------- backward: dK, dV
-template <int D, bool CAUSAL, int NS>
+template <int D, bool CAUSAL, int NS, bool BND = false>
 __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
+  static_assert(!(BND && CAUSAL), "BND: the causal bound is folded into khi / qlo");
   constexpr int DK = D / 16, DB = D / 32, TILE = KT * 2 * D, STG = 2 * TILE + 512;
   __shared__ __attribute__((aligned(16))) char lds[NS][STG];
   const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -432,8 +484,11 @@ __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
   const float c = a.scale * kLog2e;
   const int ntq64 = 2 * a.nqblk;      // rowstat tiles per (b, hq)
   const int nqt = (a.Sq + KT - 1) / KT;
-  const int qt0 = CAUSAL ? k0 / KT : 0;
-  const int per = nqt - qt0 > 0 ? nqt - qt0 : 0;
+  RowRange rg{};  // BND: the ranges of QUERIES that see the block's / the wave's / the lane's keys
+  if constexpr (BND) rg = row_range(a.qlo + b * a.bsb, a.qhi + b * a.bsb, k0, kw0, key, a.Sk, a.Sq, nqt);
+  const int qt0 = BND ? rg.t0 : (CAUSAL ? k0 / KT : 0);
+  const int qte = BND ? rg.t1 : nqt;
+  const int per = qte - qt0 > 0 ? qte - qt0 : 0;
   const int niter = gper * per;
   const bool wave_live = kw0 < kv_end;  // (wave-uniform) some key of this wave is valid
   auto stage = [&](int it, char* buf) {
@@ -452,13 +507,14 @@ __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
     __syncthreads();
     if (it + NS - 1 < niter) stage(it + NS - 1, lds[(it + NS - 1) % NS]);
     const int qt = qt0 + it % per, qs0 = qt * KT;
-    if (!wave_live || (CAUSAL && qs0 + KT - 1 < kw0)) continue;  // every query row before the wave's keys
+    // every query row before the wave's keys / outside every range of the wave
+    if (!wave_live || (BND ? (qs0 + KT <= rg.wlo || qs0 >= rg.whi) : (CAUSAL && qs0 + KT - 1 < kw0))) continue;
     const char* Qt = lds[it % NS];
     const char* Ot = Qt + TILE;  // dO
     const float* rs = reinterpret_cast<const float*>(Qt + 2 * TILE);
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
-      if (CAUSAL && qs0 + 32 * qb + 31 < kw0) continue;
+      if (BND ? (qs0 + 32 * qb + 32 <= rg.wlo || qs0 + 32 * qb >= rg.whi) : (CAUSAL && qs0 + 32 * qb + 31 < kw0)) continue;
       f32x16 s, dp;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -471,11 +527,16 @@ __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
       for (int dk = 0; dk < DK; ++dk) s = MFMA32(row_frag<D>(Qt, 32 * qb, dk, lane), kf[dk], s);
 #pragma unroll
       for (int dk = 0; dk < DK; ++dk) dp = MFMA32(row_frag<D>(Ot, 32 * qb, dk, lane), vf[dk], dp);
-      const bool msk = CAUSAL && qs0 + 32 * qb < kw0 + 31;
+      const bool msk = BND ? (qs0 + 32 * qb < rg.ilo || qs0 + 32 * qb + 32 > rg.ihi) : (CAUSAL && qs0 + 32 * qb < kw0 + 31);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         float p = fast_exp2(c * s[r]);
-        if (msk && key > qs0 + 32 * qb + crow(r, h)) p = 0.f;
+        if (BND) {
+          const int qi = qs0 + 32 * qb + crow(r, h);
+          if (msk && (qi < rg.lo || qi >= rg.hi)) p = 0.f;
+        } else if (msk && key > qs0 + 32 * qb + crow(r, h)) {
+          p = 0.f;
+        }
         s[r] = p;
         dp[r] = p * dp[r];
       }
@@ -528,21 +589,21 @@ __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
 
 // Register budgets: the head-dim-64 backward kernels fit two waves per SIMD (<= 256 registers);
 // the head-dim-128 ones would spill there, so they keep one wave per SIMD and every register.
-template <int D, bool CAUSAL, int NS = 2>
+template <int D, bool CAUSAL, int NS = 2, bool BND = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_dq(Args a) {
-  attn_dq_body<D, CAUSAL, NS>(a);
+  attn_dq_body<D, CAUSAL, NS, BND>(a);
 }
-template <int D, bool CAUSAL, int NS = 2>
+template <int D, bool CAUSAL, int NS = 2, bool BND = false>
 __global__ __launch_bounds__(256) void k_attn_dq_wide(Args a) {
-  attn_dq_body<D, CAUSAL, NS>(a);
+  attn_dq_body<D, CAUSAL, NS, BND>(a);
 }
-template <int D, bool CAUSAL, int NS = 2>
+template <int D, bool CAUSAL, int NS = 2, bool BND = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_dkdv(Args a) {
-  attn_dkdv_body<D, CAUSAL, NS>(a);
+  attn_dkdv_body<D, CAUSAL, NS, BND>(a);
 }
-template <int D, bool CAUSAL, int NS = 2>
+template <int D, bool CAUSAL, int NS = 2, bool BND = false>
 __global__ __launch_bounds__(256) void k_attn_dkdv_wide(Args a) {
-  attn_dkdv_body<D, CAUSAL, NS>(a);
+  attn_dkdv_body<D, CAUSAL, NS, BND>(a);
 }
 
 // dK / dV of a split GQA group: sum the slices in order (deterministic), cast to bf16 into the
@@ -610,6 +671,22 @@ Args make_args(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, bo
   return a;
 }
 
+bool given(const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); }
+
+// row-range arrays of the BND kernels: int32 [B or 1, S] on q's device, last dim contiguous, all
+// of one batch stride; self-attention only.  Monotonicity is trusted (checking it would sync).
+const int* bound_ptr(Args& a, const at::Tensor& q, const at::Tensor& t, const char* name, bool first) {
+  TORCH_CHECK(a.Sq == a.Sk, "attn: row-range bounds need Sq == Sk");
+  TORCH_CHECK(t.is_cuda() && t.device() == q.device() && t.scalar_type() == at::kInt && t.dim() == 2 &&
+                  (t.size(0) == a.B || t.size(0) == 1) && t.size(1) == a.Sq && t.stride(1) == 1,
+              "attn: ", name, " must be int32 [B or 1, S] on the device with a contiguous last dim");
+  const int64_t bs = t.size(0) == 1 ? 0 : t.stride(0);
+  TORCH_CHECK(bs >= 0, "attn: ", name, " batch stride");
+  TORCH_CHECK(first || bs == a.bsb, "attn: klo / khi / qlo / qhi must share one shape and batch stride");
+  a.bsb = bs;
+  return t.data_ptr<int>();
+}
+
 }  // namespace
 
 // LDS stages of the streamed tiles: 2 (HIPPS_ATTN_STAGES=3: the three-stage form, A/B).  Measured
@@ -627,11 +704,20 @@ int attn_stages(bool causal, bool backward) {
   return env == 3 ? 3 : 2;
 }
 
-#define ATTN_DISPATCH2(KER64, KER128, D_, CAUSAL_, BWD_, GRID, A)                                 \
+// BND_: the row-range kernels (causal already folded into the ranges; A.rev keeps the launch order)
+#define ATTN_DISPATCH2(KER64, KER128, D_, CAUSAL_, BWD_, BND_, GRID, A)                           \
   do {                                                                                             \
     auto st = c10::hip::getCurrentHIPStream();                                                     \
     const bool s3 = attn::attn_stages(CAUSAL_, BWD_) == 3;                                         \
-    if ((D_) == 64) {                                                                              \
+    if (BND_) {                                                                                    \
+      if ((D_) == 64) {                                                                            \
+        if (s3) hipLaunchKernelGGL((KER64<64, false, 3, true>), dim3(GRID), dim3(256), 0, st, A);   \
+        else hipLaunchKernelGGL((KER64<64, false, 2, true>), dim3(GRID), dim3(256), 0, st, A);      \
+      } else {                                                                                     \
+        if (s3) hipLaunchKernelGGL((KER128<128, false, 3, true>), dim3(GRID), dim3(256), 0, st, A); \
+        else hipLaunchKernelGGL((KER128<128, false, 2, true>), dim3(GRID), dim3(256), 0, st, A);    \
+      }                                                                                            \
+    } else if ((D_) == 64) {                                                                       \
       if (CAUSAL_) {                                                                               \
         if (s3) hipLaunchKernelGGL((KER64<64, true, 3>), dim3(GRID), dim3(256), 0, st, A);          \
         else hipLaunchKernelGGL((KER64<64, true, 2>), dim3(GRID), dim3(256), 0, st, A);             \
@@ -649,15 +735,25 @@ int attn_stages(bool causal, bool backward) {
       }                                                                                            \
     }                                                                                              \
   } while (0)
-#define ATTN_DISPATCH(KER, D_, CAUSAL_, GRID, A) ATTN_DISPATCH2(KER, KER, D_, CAUSAL_, false, GRID, A)
+#define ATTN_DISPATCH(KER, D_, CAUSAL_, BND_, GRID, A) ATTN_DISPATCH2(KER, KER, D_, CAUSAL_, false, BND_, GRID, A)
 
 }  // namespace attn
 
 // o = softmax(q k^T * scale + mask) v  for q [B, Sq, Hq, D], k / v [B, Sk, Hkv, D] (bf16);
-// returns (o [B, Sq, Hq, D] contiguous, lse [B, Hq, Sq] f32 natural log)
+// returns (o [B, Sq, Hq, D] contiguous, lse [B, Hq, Sq] f32 natural log).  klo / khi (both or
+// neither; int32 [B or 1, S]): query i sees only keys [klo[i], khi[i]), ANDed with kv_len; the
+// causal bound must already be in khi (``causal`` then only orders the launch)
 std::vector<at::Tensor> attn_forward(at::Tensor q, at::Tensor k, at::Tensor v, bool causal, double scale,
-                                     c10::optional<at::Tensor> kvlen) {
+                                     c10::optional<at::Tensor> kvlen, c10::optional<at::Tensor> klo,
+                                     c10::optional<at::Tensor> khi) {
   attn::Args a = attn::make_args(q, k, v, causal, scale, kvlen);
+  const bool bnd = attn::given(klo) || attn::given(khi);
+  if (bnd) {
+    TORCH_CHECK(attn::given(klo) && attn::given(khi), "attn: klo and khi come together");
+    a.klo = attn::bound_ptr(a, q, *klo, "klo", true);
+    a.khi = attn::bound_ptr(a, q, *khi, "khi", false);
+    a.rev = causal;
+  }
   const int64_t D = q.size(3);
   at::Tensor o = at::empty({q.size(0), q.size(1), q.size(2), D}, q.options());
   at::Tensor lse = at::empty({q.size(0), q.size(2), q.size(1)}, q.options().dtype(at::kFloat));
@@ -667,7 +763,7 @@ std::vector<at::Tensor> attn_forward(at::Tensor q, at::Tensor k, at::Tensor v, b
   a.nblk = a.nqblk = (a.Sq + attn::QB - 1) / attn::QB;
   const int64_t grid = (int64_t)a.nblk * a.B * a.Hq;
   TORCH_CHECK(grid < (int64_t(1) << 31), "attn: grid");
-  ATTN_DISPATCH(attn::k_attn_fwd, D, causal, (unsigned)grid, a);
+  ATTN_DISPATCH(attn::k_attn_fwd, D, causal, bnd, (unsigned)grid, a);
   return {o, lse};
 }
 
@@ -675,8 +771,21 @@ std::vector<at::Tensor> attn_forward(at::Tensor q, at::Tensor k, at::Tensor v, b
 std::vector<at::Tensor> attn_backward(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                       at::Tensor lse, bool causal, double scale, c10::optional<at::Tensor> kvlen,
                                       c10::optional<at::Tensor> dq_out, c10::optional<at::Tensor> dk_out,
-                                      c10::optional<at::Tensor> dv_out) {
+                                      c10::optional<at::Tensor> dv_out, c10::optional<at::Tensor> klo,
+                                      c10::optional<at::Tensor> khi, c10::optional<at::Tensor> qlo,
+                                      c10::optional<at::Tensor> qhi) {
   attn::Args a = attn::make_args(q, k, v, causal, scale, kvlen);
+  // the row ranges the forward ran with, and their transpose (key j is seen by queries [qlo[j], qhi[j]))
+  const bool bnd = attn::given(klo) || attn::given(khi) || attn::given(qlo) || attn::given(qhi);
+  if (bnd) {
+    TORCH_CHECK(attn::given(klo) && attn::given(khi) && attn::given(qlo) && attn::given(qhi),
+                "attn: klo, khi, qlo and qhi come together");
+    a.klo = attn::bound_ptr(a, q, *klo, "klo", true);
+    a.khi = attn::bound_ptr(a, q, *khi, "khi", false);
+    a.qlo = attn::bound_ptr(a, q, *qlo, "qlo", false);
+    a.qhi = attn::bound_ptr(a, q, *qhi, "qhi", false);
+    a.rev = causal;
+  }
   attn::check_qkv(dout, "dout");
   attn::check_qkv(o, "o");
   TORCH_CHECK(dout.sizes() == q.sizes() && o.sizes() == q.sizes(), "attn: dout / o shapes");
@@ -711,7 +820,7 @@ std::vector<at::Tensor> attn_backward(at::Tensor dout, at::Tensor q, at::Tensor 
   at::Tensor rowstat = at::empty({(int64_t)a.B * a.Hq * 2 * a.nblk * 128}, q.options().dtype(at::kFloat));
   a.rowstat = rowstat.data_ptr<float>();
   const int64_t gq = (int64_t)a.nblk * a.B * a.Hq;
-  ATTN_DISPATCH2(attn::k_attn_dq, attn::k_attn_dq_wide, D, causal, true, (unsigned)gq, a);
+  ATTN_DISPATCH2(attn::k_attn_dq, attn::k_attn_dq_wide, D, causal, true, bnd, (unsigned)gq, a);
   // dK / dV: split the GQA group over workgroups when the (batch, kv head, key block) grid is
   // small: under the causal mask the first key block of a sequence sweeps every query tile and
   // the last one a single tile, so a grid that fits the GPU in one wave runs as long as its
@@ -730,7 +839,7 @@ std::vector<at::Tensor> attn_backward(at::Tensor dout, at::Tensor q, at::Tensor 
   }
   a.nblk = nkb;
   const int64_t gk = (int64_t)nkb * a.B * a.Hkv * gsplit;
-  ATTN_DISPATCH2(attn::k_attn_dkdv, attn::k_attn_dkdv_wide, D, causal, true, (unsigned)gk, a);
+  ATTN_DISPATCH2(attn::k_attn_dkdv, attn::k_attn_dkdv_wide, D, causal, true, bnd, (unsigned)gk, a);
   if (gsplit > 1) {
     const int64_t n = dk.numel();
     const int grid = (int)std::min<int64_t>(2048, (2 * n / 4 + 255) / 256);

@@ -11,7 +11,8 @@
   *-tiny      same code, small widths, for CPU tests.
 
 Attention is ``hipps.ops.nn.attention`` (csrc/attn.hip: MFMA flash attention, forward and a
-deterministic backward, causal + grouped-query heads for Llama, key padding for BERT) on the
+deterministic backward, causal + grouped-query heads for Llama, key padding for BERT, packed
+documents (``doc_ids``) for both and a sliding window (``LlamaConfig.window``)) on the
 [B, S, H, hd] views of the projection outputs (no transposes); the
 projections and MLPs are ``hipps.ops.nn.Linear`` (per shape hipBLASLt or the hipps gemm2 cores,
 reading the engine's bf16 weight shadow, fp32 weight gradients written directly, the residual add
@@ -76,7 +77,7 @@ class BertLayer(nn.Module):
         # epilogue: qkv's and inter's add the residual's gradient, out's the GELU backward
         hnn.mark_transposed_reader(self.qkv.weight, self.inter.weight, self.out.weight)
 
-    def forward(self, x, mask=None):
+    def forward(self, x, mask=None, bounds=None):
         B, S, D = x.shape
         h = self.heads
 
@@ -85,8 +86,12 @@ class BertLayer(nn.Module):
         if mask is None or (torch.is_tensor(mask) and mask.dtype == torch.int32 and mask.dim() == 1):
             # the packed [B, S, 3, H, hd] projection straight into the hipps flash-attention
             # kernels (csrc/attn.hip); ``mask`` may be the int32 [B] key lengths of a padded batch
-            a = hnn.attention_qkv(qkv, kv_len=mask)
+            # (``bounds``: the packed-document mask, hnn.attention_bounds)
+            a = hnn.attention_qkv(qkv, kv_len=mask, bounds=bounds)
         else:
+            if bounds is not None:  # the documents join the SDPA mask
+                dense = bounds.dense_mask(x.device)[:, None]
+                mask = mask & dense if mask.dtype == torch.bool else mask.masked_fill(~dense, -math.inf)
             q, k, v = (t.transpose(1, 2) for t in qkv.unbind(2))
             a = F.scaled_dot_product_attention(q, k, v, attn_mask=mask).transpose(1, 2)
         a = a.reshape(B, S, D)
@@ -122,9 +127,12 @@ class Bert(nn.Module):
         if isinstance(m, nn.Linear) and m.bias is not None:
             nn.init.zeros_(m.bias)
 
-    def forward(self, ids, labels=None, kv_len=None):
-        """``kv_len``: optional int32 [B] valid lengths of a right-padded batch (key padding mask)."""
+    def forward(self, ids, labels=None, kv_len=None, doc_ids=None):
+        """``kv_len``: optional int32 [B] valid lengths of a right-padded batch (key padding mask).
+        ``doc_ids``: optional [B, S] document of each token of a packed row (a change starts a new
+        document): no token attends across a boundary."""
         B, S = ids.shape
+        bounds = hnn.attention_bounds(S, doc_ids=doc_ids, batch=B, device=ids.device)  # once, for every layer
         if (torch.is_tensor(kv_len) and kv_len.dim() == 1
                 and kv_len.dtype in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)):
             # integer lengths of any width (torch.tensor([...]) is int64) are key lengths: the layers
@@ -138,7 +146,7 @@ class Bert(nn.Module):
             x = self.word(ids) + self.pos(pos)[None] + self.tok_type(torch.zeros_like(ids))
         x = _ln(self.emb_ln, x)
         for layer in self.layers:
-            x = layer(x, kv_len)
+            x = layer(x, kv_len, bounds)
         pooled = torch.tanh(self.pooler(x[:, 0]))
         if not self.mlm:
             return x, pooled
@@ -161,6 +169,7 @@ class LlamaConfig:
     eps: float = 1e-5
     theta: float = 500000.0
     max_seq: int = 8192
+    window: int = 0  # sliding attention window (the last ``window`` keys, the query included); 0: none
 
 
 class RMSNorm(nn.Module):
@@ -216,10 +225,11 @@ class LlamaBlock(nn.Module):
         self.attn_norm = RMSNorm(c.dim, c.eps)
         self.ffn_norm = RMSNorm(c.dim, c.eps)
 
-    def forward(self, x, cos, sin, y=None):
+    def forward(self, x, cos, sin, y=None, bounds=None):
         """Returns (x', y') with the block's output = x' + y': the residual add of each branch is
         deferred into the norm that reads it next (RMSNorm(x, add=...)), so ``y`` is the previous
-        block's pending branch output (None for the first block)."""
+        block's pending branch output (None for the first block).  ``bounds``: the packed-document /
+        sliding-window mask (hnn.attention_bounds, causal)."""
         B, S, D = x.shape
         c = self.c
         hd = D // c.heads
@@ -230,12 +240,12 @@ class LlamaBlock(nn.Module):
         y = self.wqkv(h)  # [B, S, (heads + 2 kv_heads) * hd]
         if hnn.rope_attention_packed_ok(y, cos, c.heads, c.kv_heads):
             # RoPE + causal GQA flash attention on the packed projection (csrc/act.hip, attn.hip)
-            a = hnn.rope_attention_packed(y, cos, sin, c.heads, c.kv_heads)
+            a = hnn.rope_attention_packed(y, cos, sin, c.heads, c.kv_heads, bounds=bounds)
         else:
             q, k, v = y.split([c.heads * hd, c.kv_heads * hd, c.kv_heads * hd], dim=-1)
             q = _rope(q.reshape(B, S, c.heads, hd).contiguous(), cos, sin)
             k = _rope(k.reshape(B, S, c.kv_heads, hd).contiguous(), cos, sin)
-            a = hnn.attention(q, k, v.reshape(B, S, c.kv_heads, hd), causal=True)
+            a = hnn.attention(q, k, v.reshape(B, S, c.kv_heads, hd), causal=True, bounds=bounds)
         x, h = self.ffn_norm(x, add=self.wo(a.reshape(B, S, D)))
         return x, self.w2(hnn.swiglu_packed(self.w13(h)))
 
@@ -264,13 +274,18 @@ class Llama(nn.Module):
             cache[key] = (f.cos().contiguous(), f.sin().contiguous())
         return cache[key]
 
-    def forward(self, ids, labels=None):
+    def forward(self, ids, labels=None, doc_ids=None):
+        """``doc_ids``: optional [B, S] document of each token of a packed row (a change starts a new
+        document): no token attends across a boundary (RoPE is relative: positions are not reset)."""
         B, S = ids.shape
         x = self.tok(ids)
         cos, sin = self.rope_tables(S, ids.device)
+        # once, for every block (None without documents and window: the plain causal kernels)
+        bounds = hnn.attention_bounds(S, doc_ids=doc_ids, window=self.c.window or None, causal=True, batch=B,
+                                      device=ids.device)
         y = None
         for b in self.blocks:
-            x, y = b(x, cos, sin, y)
+            x, y = b(x, cos, sin, y, bounds)
         logits = self.head(self.norm(x) if y is None else self.norm(x, add=y)[1])
         if labels is None:
             return logits

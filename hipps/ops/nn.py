@@ -13,7 +13,7 @@ models stay portable and the CPU test suite exercises the same module.
 from __future__ import annotations
 
 import collections
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -1149,8 +1149,105 @@ def _attn_rows_ok(t: torch.Tensor) -> bool:
             and all(x % 8 == 0 for x in t.stride()[:3]) and t.data_ptr() % 16 == 0)
 
 
-def attention_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False) -> bool:
-    """Whether :func:`attention` runs on the hipps kernels for these operands."""
+class AttnBounds(NamedTuple):
+    """Row-range form of a packed-document / sliding-window mask (:func:`attention_bounds`): int32
+    [B or 1, S] arrays, each non-decreasing along S.  Query i sees keys [klo[i], khi[i]); key j is
+    seen by queries [qlo[j], qhi[j]).  ``doc_ids`` / ``window`` / ``causal`` are the definition the
+    ranges were built from (the SDPA fallback builds its dense mask from them)."""
+    klo: torch.Tensor
+    khi: torch.Tensor
+    qlo: torch.Tensor
+    qhi: torch.Tensor
+    doc_ids: Optional[torch.Tensor]
+    window: Optional[int]
+    causal: bool
+
+    def to(self, device) -> "AttnBounds":
+        device = torch.device(device)
+        if self.klo.device == device:
+            return self
+        d = None if self.doc_ids is None else self.doc_ids.to(device)
+        return AttnBounds(*(t.to(device) for t in self[:4]), d, self.window, self.causal)
+
+    def dense_mask(self, device=None) -> torch.Tensor:
+        """bool [B or 1, S, S] from the definition (not from the ranges): True where query i sees
+        key j -- same document, |i - j| < window, j <= i under causal."""
+        S = self.klo.shape[1]
+        device = self.klo.device if device is None else device
+        i = torch.arange(S, device=device)
+        m = torch.ones(1, S, S, dtype=torch.bool, device=device)
+        if self.doc_ids is not None:
+            d = self.doc_ids.to(device)
+            run = torch.cat([torch.zeros_like(d[:, :1], dtype=torch.bool), d[:, 1:] != d[:, :-1]], 1).cumsum(1)
+            m = m & (run[:, :, None] == run[:, None, :])
+        if self.window is not None:
+            m = m & ((i[:, None] - i[None, :]).abs() < self.window)
+        if self.causal:
+            m = m & (i[None, :] <= i[:, None])
+        return m
+
+
+def attention_bounds(S: int, *, doc_ids: Optional[torch.Tensor] = None, window: Optional[int] = None,
+                     causal: bool = False, batch: Optional[int] = None, device=None) -> Optional[AttnBounds]:
+    """The mask of packed documents and / or a sliding window, for the ``bounds`` argument of
+    :func:`attention`, :func:`attention_qkv` and :func:`rope_attention_packed` (self-attention of
+    S tokens).  Query i sees key j iff
+
+      * ``doc_ids[b, i]`` and ``doc_ids[b, j]`` lie in the same document -- a maximal run of equal
+        consecutive values of ``doc_ids`` [B, S] (any change starts a new document);
+      * ``|i - j| < window`` (``window >= 1``; under ``causal`` the last ``window`` keys, i included);
+      * ``j <= i`` under ``causal`` (the call it is passed to must use the same ``causal``).
+
+    Returns None when neither mask is given.  A few torch ops on ``device`` (default: that of
+    ``doc_ids``, else the CPU): build it once per forward, not per layer.  A window alone gives
+    [1, S] arrays shared by every batch row."""
+    if doc_ids is None and window is None:
+        return None
+    if window is not None:
+        window = int(window)
+        if window < 1:
+            raise ValueError("attention_bounds: window must be >= 1")
+    S = int(S)
+    if doc_ids is not None:
+        if doc_ids.dim() != 2 or doc_ids.shape[1] != S or (batch is not None and doc_ids.shape[0] != batch):
+            raise ValueError(f"attention_bounds: doc_ids must be [batch, {S}], got {tuple(doc_ids.shape)}")
+        if device is not None:
+            doc_ids = doc_ids.to(device)
+        device = doc_ids.device
+    idx = torch.arange(S, device=device, dtype=torch.int64)[None]
+    if doc_ids is not None:
+        first = torch.cat([torch.ones_like(doc_ids[:, :1], dtype=torch.bool), doc_ids[:, 1:] != doc_ids[:, :-1]], 1)
+        last = torch.cat([first[:, 1:], torch.ones_like(first[:, :1])], 1)
+        ds = torch.where(first, idx, torch.zeros_like(idx)).cummax(1).values           # start of i's document
+        de = torch.where(last, idx + 1, torch.full_like(idx, S)).flip(1).cummin(1).values.flip(1)  # its end
+    else:
+        ds, de = torch.zeros_like(idx), torch.full_like(idx, S)
+    W = S if window is None else min(window, S)
+    klo = torch.maximum(ds, idx - W + 1)
+    qhi = torch.minimum(de, idx + W)
+    khi = (idx + 1).expand_as(klo) if causal else qhi
+    qlo = idx.expand_as(klo) if causal else klo
+    klo, khi, qlo, qhi = (t.to(torch.int32).contiguous() for t in (klo, khi, qlo, qhi))
+    return AttnBounds(klo, khi, qlo, qhi, doc_ids, window, bool(causal))
+
+
+def _attn_bounds_for(bounds: Optional[AttnBounds], q: torch.Tensor, S: int, causal: bool) -> Optional[AttnBounds]:
+    """``bounds`` checked against the call (ValueError) and moved to q's device."""
+    if bounds is None:
+        return None
+    if bool(bounds.causal) != bool(causal):
+        raise ValueError(f"attention: bounds were built with causal={bounds.causal}, the call has causal={bool(causal)}")
+    if bounds.klo.shape[1] != S or bounds.klo.shape[0] not in (1, q.shape[0]):
+        raise ValueError(f"attention: bounds of shape {tuple(bounds.klo.shape)} for batch {q.shape[0]}, {S} tokens")
+    return bounds.to(q.device)
+
+
+def attention_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False,
+                 bounds: Optional[AttnBounds] = None) -> bool:
+    """Whether :func:`attention` runs on the hipps kernels for these operands (row-range
+    ``bounds`` are for self-attention: Sq == Sk)."""
+    if bounds is not None and q.shape[1] != k.shape[1]:
+        return False
     return (_FUSED_ATTN and _attn_rows_ok(q) and _attn_rows_ok(k) and _attn_rows_ok(v) and q.shape[3] in (64, 128)
             and k.shape == v.shape and k.shape[3] == q.shape[3] and k.shape[0] == q.shape[0]
             and q.shape[2] % k.shape[2] == 0 and (not causal or q.shape[1] == k.shape[1])
@@ -1163,20 +1260,21 @@ class _FlashAttention(torch.autograd.Function):
     the dQ and the dK/dV kernels (deterministic: no float atomics)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, kv_len):
-        o, lse = native().attn_forward(q, k, v, causal, scale, kv_len)
-        ctx.save_for_backward(q, k, v, o, lse, kv_len)
+    def forward(ctx, q, k, v, causal, scale, kv_len, bounds=None):
+        r = (None,) * 4 if bounds is None else tuple(bounds[:4])  # klo, khi, qlo, qhi
+        o, lse = native().attn_forward(q, k, v, causal, scale, kv_len, r[0], r[1])
+        ctx.save_for_backward(q, k, v, o, lse, kv_len, *r)
         ctx.causal, ctx.scale = causal, scale
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse, kv_len = ctx.saved_tensors
+        q, k, v, o, lse, kv_len, *r = ctx.saved_tensors
         do = do.to(torch.bfloat16)
         if not _attn_rows_ok(do):
             do = do.contiguous()
-        dq, dk, dv = native().attn_backward(do, q, k, v, o, lse, ctx.causal, ctx.scale, kv_len)
-        return dq, dk, dv, None, None, None
+        dq, dk, dv = native().attn_backward(do, q, k, v, o, lse, ctx.causal, ctx.scale, kv_len, None, None, None, *r)
+        return dq, dk, dv, None, None, None, None
 
 
 class _FlashAttentionQKV(torch.autograd.Function):
@@ -1187,36 +1285,40 @@ class _FlashAttentionQKV(torch.autograd.Function):
     three separate views."""
 
     @staticmethod
-    def forward(ctx, qkv, causal, scale, kv_len):
+    def forward(ctx, qkv, causal, scale, kv_len, bounds=None):
         q, k, v = qkv.unbind(2)
-        o, lse = native().attn_forward(q, k, v, causal, scale, kv_len)
-        ctx.save_for_backward(qkv, o, lse, kv_len)
+        r = (None,) * 4 if bounds is None else tuple(bounds[:4])
+        o, lse = native().attn_forward(q, k, v, causal, scale, kv_len, r[0], r[1])
+        ctx.save_for_backward(qkv, o, lse, kv_len, *r)
         ctx.causal, ctx.scale = causal, scale
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse, kv_len = ctx.saved_tensors
+        qkv, o, lse, kv_len, *r = ctx.saved_tensors
         do = do.to(torch.bfloat16)
         if not _attn_rows_ok(do):
             do = do.contiguous()
         g = torch.empty(qkv.shape, dtype=torch.bfloat16, device=qkv.device)
         q, k, v = qkv.unbind(2)
         gq, gk, gv = g.unbind(2)
-        native().attn_backward(do, q, k, v, o, lse, ctx.causal, ctx.scale, kv_len, gq, gk, gv)
-        return g, None, None, None
+        native().attn_backward(do, q, k, v, o, lse, ctx.causal, ctx.scale, kv_len, gq, gk, gv, *r)
+        return g, None, None, None, None
 
 
 def attention_qkv(qkv: torch.Tensor, causal: bool = False, scale: Optional[float] = None,
-                  kv_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  kv_len: Optional[torch.Tensor] = None, bounds: Optional[AttnBounds] = None) -> torch.Tensor:
     """:func:`attention` of q, k, v packed as ``qkv`` [B, S, 3, H, D] (e.g. ``linear(x, W_qkv)
     .view(B, S, 3, H, D)``); returns [B, S, H, D]."""
     q, k, v = qkv.unbind(2)
-    if attention_ok(q, k, v, causal) and qkv.dtype == torch.bfloat16:
+    bounds = _attn_bounds_for(bounds, q, q.shape[1], causal)
+    if attention_ok(q, k, v, causal, bounds) and qkv.dtype == torch.bfloat16:
         sc = float(scale) if scale is not None else 1.0 / (qkv.shape[-1] ** 0.5)
         kl = None if kv_len is None else kv_len.to(device=qkv.device, dtype=torch.int32).contiguous()
-        return _FlashAttentionQKV.apply(qkv, bool(causal), sc, kl)
-    return attention(q, k, v, causal=causal, scale=scale, kv_len=kv_len)
+        if bounds is None:
+            return _FlashAttentionQKV.apply(qkv, bool(causal), sc, kl)
+        return _FlashAttentionQKV.apply(qkv, bool(causal), sc, kl, bounds)
+    return attention(q, k, v, causal=causal, scale=scale, kv_len=kv_len, bounds=bounds)
 
 
 class _RopeAttentionPacked(torch.autograd.Function):
@@ -1228,7 +1330,7 @@ class _RopeAttentionPacked(torch.autograd.Function):
     three views of y."""
 
     @staticmethod
-    def forward(ctx, y, cos, sin, hq, hkv, causal, scale):
+    def forward(ctx, y, cos, sin, hq, hkv, causal, scale, bounds=None):
         B, S, W = y.shape
         D = W // (hq + 2 * hkv)
         y2 = y.view(B * S, W)
@@ -1238,14 +1340,15 @@ class _RopeAttentionPacked(torch.autograd.Function):
         C.rope_apply(y2[:, :hq * D], q.view(B * S, hq * D), cos, sin, S, D, 1.0)
         C.rope_apply(y2[:, hq * D:(hq + hkv) * D], k.view(B * S, hkv * D), cos, sin, S, D, 1.0)
         v = y[:, :, (hq + hkv) * D:].view(B, S, hkv, D)
-        o, lse = C.attn_forward(q, k, v, causal, scale, None)
-        ctx.save_for_backward(q, k, y, o, lse, cos, sin)
+        r = (None,) * 4 if bounds is None else tuple(bounds[:4])
+        o, lse = C.attn_forward(q, k, v, causal, scale, None, r[0], r[1])
+        ctx.save_for_backward(q, k, y, o, lse, cos, sin, *r)
         ctx.meta = (hq, hkv, D, causal, scale)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, y, o, lse, cos, sin = ctx.saved_tensors
+        q, k, y, o, lse, cos, sin, *r = ctx.saved_tensors
         hq, hkv, D, causal, scale = ctx.meta
         B, S, W = y.shape
         do = do.to(torch.bfloat16)
@@ -1257,11 +1360,11 @@ class _RopeAttentionPacked(torch.autograd.Function):
         gk = g[:, :, hq * D:(hq + hkv) * D].view(B, S, hkv, D)
         gv = g[:, :, (hq + hkv) * D:].view(B, S, hkv, D)
         C = native()
-        C.attn_backward(do, q, k, v, o, lse, causal, scale, None, gq, gk, gv)
+        C.attn_backward(do, q, k, v, o, lse, causal, scale, None, gq, gk, gv, *r)
         g2 = g.view(B * S, W)
         for a, b in ((0, hq * D), (hq * D, (hq + hkv) * D)):  # rotate back in place (the backward of RoPE)
             C.rope_apply(g2[:, a:b], g2[:, a:b], cos, sin, S, D, -1.0)
-        return g, None, None, None, None, None, None
+        return g, None, None, None, None, None, None, None
 
 
 def rope_attention_packed_ok(y: torch.Tensor, cos: torch.Tensor, hq: int, hkv: int) -> bool:
@@ -1275,34 +1378,59 @@ def rope_attention_packed_ok(y: torch.Tensor, cos: torch.Tensor, hq: int, hkv: i
 
 
 def rope_attention_packed(y: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, hq: int, hkv: int,
-                          causal: bool = True, scale: Optional[float] = None) -> torch.Tensor:
+                          causal: bool = True, scale: Optional[float] = None,
+                          bounds: Optional[AttnBounds] = None) -> torch.Tensor:
     """Rotary embedding + (causal, grouped-query) attention of a packed q | k | v projection
-    y [B, S, (hq + 2 hkv) * D]; returns [B, S, hq, D].  Callers check rope_attention_packed_ok."""
+    y [B, S, (hq + 2 hkv) * D]; returns [B, S, hq, D].  Callers check rope_attention_packed_ok.
+    ``bounds``: :func:`attention_bounds` (RoPE is relative: no position reset per document)."""
     D = y.shape[-1] // (hq + 2 * hkv)
     sc = float(scale) if scale is not None else 1.0 / (D ** 0.5)
-    return _RopeAttentionPacked.apply(y, cos, sin, int(hq), int(hkv), bool(causal), sc)
+    bounds = _attn_bounds_for(bounds, y, y.shape[1], causal)
+    if bounds is None:
+        return _RopeAttentionPacked.apply(y, cos, sin, int(hq), int(hkv), bool(causal), sc)
+    return _RopeAttentionPacked.apply(y, cos, sin, int(hq), int(hkv), bool(causal), sc, bounds)
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False,
-              scale: Optional[float] = None, kv_len: Optional[torch.Tensor] = None) -> torch.Tensor:
+              scale: Optional[float] = None, kv_len: Optional[torch.Tensor] = None,
+              bounds: Optional[AttnBounds] = None) -> torch.Tensor:
     """Scaled dot-product attention on the [batch, seq, heads, head_dim] layout (the projection
     outputs viewed per head, no transposes): q [B, Sq, Hq, D], k / v [B, Sk, Hkv, D] with Hq a
     multiple of Hkv (grouped-query attention), optional causal mask (Sq == Sk) and key padding
-    (``kv_len`` int32 [B]: keys >= kv_len[b] are masked).  Returns [B, Sq, Hq, D].
+    (``kv_len`` int32 [B]: keys >= kv_len[b] are masked).  ``bounds`` (:func:`attention_bounds`,
+    built with the same ``causal``) adds a packed-document and / or sliding-window mask, ANDed
+    with the others; a query row left with no key gives o = 0 and no gradient.  Returns
+    [B, Sq, Hq, D].
 
-    bf16 device operands with head dim 64 / 128 run the hipps flash-attention kernels; anything
-    else runs ``F.scaled_dot_product_attention`` on the transposed views."""
+    bf16 device operands with head dim 64 / 128 run the hipps flash-attention kernels (which skip
+    the key tiles outside a row's document / window); anything else runs
+    ``F.scaled_dot_product_attention`` on the transposed views."""
     D = q.shape[-1]
     sc = float(scale) if scale is not None else 1.0 / (D ** 0.5)
-    if attention_ok(q, k, v, causal):
+    bounds = _attn_bounds_for(bounds, q, k.shape[1], causal)
+    if attention_ok(q, k, v, causal, bounds):
         kl = None
         if kv_len is not None:
             kl = kv_len.to(device=q.device, dtype=torch.int32).contiguous()
-        return _FlashAttention.apply(q, k, v, bool(causal), sc, kl)
+        if bounds is None:
+            return _FlashAttention.apply(q, k, v, bool(causal), sc, kl)
+        return _FlashAttention.apply(q, k, v, bool(causal), sc, kl, bounds)
     qt, kt, vt = (t.transpose(1, 2) for t in (q, k, v))
     if k.shape[2] != q.shape[2]:
         rep = q.shape[2] // k.shape[2]
         kt, vt = kt.repeat_interleave(rep, dim=1), vt.repeat_interleave(rep, dim=1)
+    if bounds is not None:
+        if q.shape[1] != k.shape[1]:
+            raise ValueError("attention: bounds are for self-attention (Sq == Sk)")
+        mask = bounds.dense_mask(q.device)  # (causal included)
+        if kv_len is not None:
+            keys = torch.arange(k.shape[1], device=q.device)
+            mask = mask & (keys[None, :] < kv_len.to(q.device).view(-1, 1))[:, None, :]
+        mask = mask[:, None]
+        # a row with no key: SDPA would give NaN; attend anywhere and select 0 (no gradient either)
+        live = mask.any(-1, keepdim=True)
+        o = F.scaled_dot_product_attention(qt, kt, vt, attn_mask=mask | ~live, scale=sc)
+        return torch.where(live, o, torch.zeros_like(o)).transpose(1, 2)
     mask = None
     if kv_len is not None:
         keys = torch.arange(k.shape[1], device=q.device)

@@ -367,12 +367,14 @@ def _bf16_round(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.bfloat16).to(torch.float64)
 
 
-def attention(q, k, v, dout, causal=False, kv_len=None, scale=None, emulate_bf16=False):
+def attention(q, k, v, dout, causal=False, kv_len=None, scale=None, emulate_bf16=False, doc_ids=None, window=None):
     """fp64 oracle of csrc/attn.hip, forward and an explicit (no autograd) backward.
 
     q / dout [B, Sq, Hq, D], k / v [B, Sk, Hkv, D] (GQA by repetition: query head h reads kv head
     h // (Hq / Hkv)); ``causal`` masks key > query row, ``kv_len`` [B] masks key >= kv_len[b]
-    (values above Sk behave as Sk).  Returns fp64 (o [B, Sq, Hq, D], lse [B, Hq, Sq], dq, dk, dv).
+    (values above Sk behave as Sk).  Self-attention only: ``doc_ids`` [B, S] masks every key outside
+    the query's document (a maximal run of equal consecutive values), ``window`` every key with
+    |query - key| >= window.  Returns fp64 (o [B, Sq, Hq, D], lse [B, Hq, Sq], dq, dk, dv).
     A row with every key masked has o = 0, lse = +inf and contributes no gradient.
 
     ``emulate_bf16`` rounds to bf16 where the kernels do and nowhere else: exp(s - rowmax) before
@@ -394,6 +396,16 @@ def attention(q, k, v, dout, causal=False, kv_len=None, scale=None, emulate_bf16
     if kv_len is not None:
         kl = torch.as_tensor(kv_len, device=q.device).view(B, 1, 1, 1)
         mask = mask & (keys < kl)
+    if doc_ids is not None or window is not None:
+        assert Sq == Sk, "doc_ids / window: self-attention only"
+    if doc_ids is not None:
+        d = torch.as_tensor(doc_ids, device=q.device).view(B, Sk)
+        doc = torch.zeros_like(d)  # the index of each token's run
+        for j in range(1, Sk):
+            doc[:, j] = doc[:, j - 1] + (d[:, j] != d[:, j - 1]).to(doc.dtype)
+        mask = mask & (doc[:, None, :, None] == doc[:, None, None, :])
+    if window is not None:
+        mask = mask & ((keys[:, None] - keys[None, :]).abs() < int(window))
     mask = mask.expand(B, Hq, Sq, Sk)
     s = (qd @ kd.transpose(-1, -2)) * sc
     live = mask.any(-1, keepdim=True)

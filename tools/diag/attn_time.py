@@ -2,6 +2,15 @@
 transformer configs' attention shapes, forward and backward, same process, interleaved.
 
     python tools/diag/attn_time.py [--json out.json]
+
+With ``--docs N`` (N equal documents per row) and / or ``--window W`` it times the row-range
+(BND) kernels with that mask against the unbounded kernels instead, and prints next to each time
+the (wave, 64-row tile) pairs the mask leaves the kernels to visit -- forward / dQ: per 32 query
+rows the key tiles that meet the union of their key ranges; dK/dV: per 32 keys the query tiles
+likewise -- so the time ratio can be held against the tile ratio.  ``--docs 1`` is one document:
+every tile of the unbounded kernels, plus the loads of the bounds.
+
+    python tools/diag/attn_time.py --docs 8 [--window 512] [--json out.json]
 """
 import argparse
 import json
@@ -23,7 +32,11 @@ SHAPES = {
 }
 
 
-def _time(fn, n=10):
+ITERS = 10
+
+
+def _time(fn, n=None):
+    n = n or ITERS
     for _ in range(3):
         fn()
     torch.cuda.synchronize()
@@ -38,11 +51,77 @@ def _time(fn, n=10):
     return sorted(ts)[n // 2]
 
 
+def _tiles(lo, hi):
+    """(wave, tile) pairs over a [B or 1, S] pair of range arrays: per run of 32 rows the 64-row
+    tiles that meet [lo[first], hi[last]) (what the kernels' wave-uniform skip leaves)."""
+    S = lo.shape[1]
+    first = torch.arange(0, S, 32)
+    last = (first + 31).clamp(max=S - 1)
+    a, b = lo[:, first].long(), hi[:, last].long()
+    return int(((b + 63) // 64 - a // 64).clamp(min=0)[b > a].sum()) / lo.shape[0]
+
+
+def _mask_tiles(bd):
+    """Visited tiles per (batch row, head) of the forward (= dQ) and the dK/dV kernels."""
+    bd = bd.to("cpu")
+    return _tiles(bd.klo, bd.khi), _tiles(bd.qlo, bd.qhi)
+
+
+def _masked(a):
+    """--docs / --window: the bounded kernels against the unbounded ones, with tile counts."""
+    out = {}
+    for name, (B, S, Hq, Hkv, D, causal) in SHAPES.items():
+        if a.only and a.only not in name:
+            continue
+        torch.manual_seed(0)
+        q = torch.randn(B, S, Hq, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+        k = torch.randn(B, S, Hkv, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+        v = torch.randn(B, S, Hkv, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+        g = torch.randn(B, S, Hq, D, device="cuda", dtype=torch.bfloat16)
+        doc_ids = None
+        if a.docs:
+            doc_ids = (torch.arange(S, device="cuda") * a.docs // S)[None].expand(B, S).contiguous()
+        bd = hnn.attention_bounds(S, doc_ids=doc_ids, window=a.window or None, causal=causal, device="cuda")
+        full = hnn.attention_bounds(S, window=S, causal=causal)  # the ranges of the unbounded kernels
+        row = {}
+        for tag, b in (("unbounded", None), ("masked", bd)):
+            f = lambda b=b: hnn.attention(q, k, v, causal=causal, bounds=b)  # noqa: E731
+            with torch.no_grad():
+                tf = _time(f)
+            o = f()
+            tb = _time(lambda: torch.autograd.grad(o, (q, k, v), g, retain_graph=True))
+            tq, tk = _mask_tiles(full if b is None else b)
+            row[tag] = {"fwd_ms": round(tf, 4), "bwd_ms": round(tb, 4), "fwd_tiles": tq, "bwd_tiles": tq + tk}
+        m, u = row["masked"], row["unbounded"]
+        row["ratio"] = {x: round(m[x] / u[x], 4) for x in ("fwd_ms", "fwd_tiles", "bwd_ms", "bwd_tiles")}
+        out[name] = row
+        r = row["ratio"]
+        print(f"{name:16s} fwd {u['fwd_ms']:.3f} -> {m['fwd_ms']:.3f} ms (x{r['fwd_ms']:.3f}; tiles "
+              f"{u['fwd_tiles']:.0f} -> {m['fwd_tiles']:.0f}, x{r['fwd_tiles']:.3f}) | bwd {u['bwd_ms']:.3f} -> "
+              f"{m['bwd_ms']:.3f} ms (x{r['bwd_ms']:.3f}; tiles {u['bwd_tiles']:.0f} -> {m['bwd_tiles']:.0f}, "
+              f"x{r['bwd_tiles']:.3f})", flush=True)
+        del q, k, v, g
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
+    global ITERS
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
     ap.add_argument("--only", default=None)
+    ap.add_argument("--docs", type=int, default=0, help="N equal documents per row (row-range kernels)")
+    ap.add_argument("--window", type=int, default=0, help="sliding window of W keys (row-range kernels)")
+    ap.add_argument("--iters", type=int, default=ITERS, help="timed calls per figure (the median is kept)")
     a = ap.parse_args()
+    ITERS = a.iters
+    if a.docs or a.window:
+        out = _masked(a)
+        if a.json:
+            os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
+            with open(a.json, "w") as f:
+                json.dump({"docs": a.docs, "window": a.window, "shapes": out}, f, indent=1)
+        return
     out = {}
     for name, (B, S, Hq, Hkv, D, causal) in SHAPES.items():
         if a.only and a.only not in name:

@@ -35,6 +35,13 @@
 // streams only the tiles its rows can see and a wave masks per element only at a range's edge
 // (RowRange below).  BND = false compiles to the plain kernels unchanged.
 //
+// Dropout of the attention probabilities (the DROP instantiations, two LDS stages): P is never
+// stored, so forward, dQ and dK/dV each regenerate the mask from common.h dropout_keep(seed, b, hq,
+// i, j) -- one 64-bit hash per 2 queries x 4 keys, a function of nothing else -- and scale by
+// rinv = 1 / (1 - p_eff) in fp32: o = (sum keep P v) rinv / l, dS = P (keep rinv dP - delta),
+// dV = rinv (keep P)^T dO.  lse and delta = rowsum(dO * O) are as without dropout.  DROP = false
+// compiles to the plain kernels unchanged.
+//
 // LDS images: every tile is [rows][D] bf16 with the 16-byte chunk c of row r stored at chunk
 // c ^ f(r) -- one image serves the ds_read_b128 row reads (operand rows on the lanes) and the
 // ds_read_b64_tr_b16 transposed reads conflict-free (T10 'One image for row reads AND transposed
@@ -87,6 +94,12 @@ struct Args {
   const int *klo, *khi, *qlo, *qhi;
   int64_t bsb;  // their batch stride (0: one row for every batch)
   int rev;      // forward / dQ: launch the query blocks last-first (the heaviest first under causal)
+  // DROP kernels (attention-probability dropout): element (b, hq, i, j) of P is kept iff
+  // dropout_keep(drop_seed, kDropStreamAttn, b, hq, i, j, drop_thr) (common.h) and scaled by
+  // drop_rinv = 1 / (1 - drop_thr / 256); the three kernels regenerate the same mask
+  uint64_t drop_seed;
+  uint32_t drop_thr;
+  float drop_rinv;
 };
 
 template <int D> __device__ __forceinline__ int swz(int row) {
@@ -187,6 +200,16 @@ template <int NS> __device__ __forceinline__ void wait_tile(bool younger, int n_
 // row of accumulator register r for lane half h (32x32 C layout)
 __device__ __forceinline__ int crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
+// DROP, forward / dQ: the keep fields of query ``row`` at the 4 consecutive keys key0 .. key0 + 3
+// of one accumulator register group (key0 a multiple of 4); rowkey = head key ^ the row's half of
+// the hash counter (common.h dropout_word)
+__device__ __forceinline__ uint64_t drop_rowkey(uint64_t head_key, int row) {
+  return head_key ^ ((uint64_t)((uint32_t)row >> 1) << 32);
+}
+__device__ __forceinline__ uint32_t drop_keys4(uint64_t rowkey, int row, int key0) {
+  return dropout_row4(splitmix64(rowkey ^ (uint64_t)((uint32_t)key0 >> 2)), (uint32_t)row);
+}
+
 // 4 consecutive d values (one accumulator register group) as 8 bytes of bf16
 __device__ __forceinline__ void store4(uint16_t* p, float a, float b, float c, float d) {
   *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16x2(a, b), pack_bf16x2(c, d));
@@ -220,8 +243,13 @@ __device__ __forceinline__ RowRange row_range(const int* lo, const int* hi, int 
 }
 
 // ------------------------------------------------------------------------------------ forward
-template <int D, bool CAUSAL, int NS = 2, bool BND = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_fwd(Args a) {
+// DROP: dropped elements of P leave the P V product (the softmax statistics are those of the
+// undropped P); the 1 / (1 - p) scale folds into the final 1 / l
+// The D = 128 causal DROP form does not fit the 256 registers of two waves per SIMD (its plain twin
+// takes 250): like the D = 128 backward's _wide kernels it keeps one wave per SIMD and every register.
+template <int D, bool CAUSAL, int NS = 2, bool BND = false, bool DROP = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP && CAUSAL && D == 128 ? 1 : 2))) void
+k_attn_fwd(Args a) {
   static_assert(!(BND && CAUSAL), "BND: the causal bound is folded into khi / qlo");
   constexpr int DK = D / 16, DB = D / 32, TILE = KT * 2 * D;
   __shared__ __attribute__((aligned(16))) char lds[NS][2 * TILE];
@@ -252,6 +280,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
   float m = -INFINITY, lsum = 0.f;
   const float c = a.scale * kLog2e;
+  uint64_t rowkey = 0;
+  if constexpr (DROP) rowkey = drop_rowkey(dropout_head_key(a.drop_seed, kDropStreamAttn, b, hq), qrow);
   for (int p = 0; p < NS - 1 && it0 + p < ntile; ++p) {
     stage_tile<D>(lds[p], kb, a.kss, (it0 + p) * KT, kv_end, w, lane);
     stage_tile<D>(lds[p] + TILE, vb, a.vss, (it0 + p) * KT, kv_end, w, lane);
@@ -316,13 +346,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
+        if constexpr (DROP) {
+#pragma unroll
+          for (int g = 2 * s2; g < 2 * s2 + 2; ++g) {
+            const uint32_t f = drop_keys4(rowkey, qrow, k0 + 32 * kk + 8 * g + 4 * h);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (!dropout_keep4(f, j, a.drop_thr)) s[kk][4 * g + j] = 0.f;
+          }
+        }
         const bf16x8 pf = pack8(s[kk], s2);
 #pragma unroll
         for (int db = 0; db < DB; ++db) o[db] = MFMA32(tr_frag<D>(Vt, 32 * kk + 16 * s2, db, lane), pf, o[db]);
       }
   }
   const float lt = half_sum(lsum);
-  const float inv = lt > 0.f ? 1.f / lt : 0.f;
+  const float inv = lt > 0.f ? (DROP ? a.drop_rinv / lt : 1.f / lt) : 0.f;
   if (qrow < a.Sq) {
     uint16_t* op = a.out + b * a.osb + hq * a.osh + (int64_t)qrow * a.oss;
 #pragma unroll
@@ -338,7 +377,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 // ------------------------------------------------------------------------------- backward: dQ
 // Also computes delta = rowsum(dO * O) and publishes the per-row constants the dK/dV kernel
 // initialises its accumulators with (rowstat), so no separate preprocess pass reads dO and O.
-template <int D, bool CAUSAL, int NS, bool BND = false>
+// DROP: dS = P (keep * rinv * dP_raw - delta): the dP accumulator starts at 0 instead of -delta
+// and -delta joins after the product (delta = rowsum(dO * O) already is that of the dropped P)
+template <int D, bool CAUSAL, int NS, bool BND = false, bool DROP = false>
 __device__ __forceinline__ void attn_dq_body(const Args& a) {
   static_assert(!(BND && CAUSAL), "BND: the causal bound is folded into khi / qlo");
   constexpr int DK = D / 16, DB = D / 32, TILE = KT * 2 * D;
@@ -387,6 +428,8 @@ __device__ __forceinline__ void attn_dq_body(const Args& a) {
   for (int db = 0; db < DB; ++db)
 #pragma unroll
     for (int r = 0; r < 16; ++r) dq[db][r] = 0.f;
+  uint64_t rowkey = 0;
+  if constexpr (DROP) rowkey = drop_rowkey(dropout_head_key(a.drop_seed, kDropStreamAttn, b, hq), qrow);
   for (int p = 0; p < NS - 1 && it0 + p < ntile; ++p) {
     stage_tile<D>(lds[p], kb, a.kss, (it0 + p) * KT, kv_end, w, lane);
     stage_tile<D>(lds[p] + TILE, vb, a.vss, (it0 + p) * KT, kv_end, w, lane);
@@ -409,7 +452,7 @@ __device__ __forceinline__ void attn_dq_body(const Args& a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         s[kk][r] = 0.f;
-        dp[kk][r] = -delta;
+        dp[kk][r] = DROP ? 0.f : -delta;
       }
 #pragma unroll
       for (int dk = 0; dk < DK; ++dk) s[kk] = MFMA32(row_frag<D>(Kt, 32 * kk, dk, lane), qf[dk], s[kk]);
@@ -417,6 +460,19 @@ __device__ __forceinline__ void attn_dq_body(const Args& a) {
       for (int dk = 0; dk < DK; ++dk) dp[kk] = MFMA32(row_frag<D>(Vt, 32 * kk, dk, lane), df[dk], dp[kk]);
     }
     const bool msk = BND ? (k0 < rg.ilo || k0 + KT > rg.ihi) : (k0 + KT > kv_end || (CAUSAL && k0 + KT - 1 > qw0));
+    if constexpr (DROP) {
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const uint32_t f = drop_keys4(rowkey, qrow, k0 + 32 * kk + 8 * g + 4 * h);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int r = 4 * g + j;
+            dp[kk][r] = dropout_keep4(f, j, a.drop_thr) ? fmaf(dp[kk][r], a.drop_rinv, -delta) : -delta;
+          }
+        }
+    }
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
@@ -450,7 +506,10 @@ __device__ __forceinline__ void attn_dq_body(const Args& a) {
 }
 
 // ---------------------------------------------------------------------------- backward: dK, dV
-template <int D, bool CAUSAL, int NS, bool BND = false>
+// DROP: the lane's key is fixed and its accumulator registers run over queries; the head in the
+// hash is the query head of the GQA loop.  dV^T += dO^T (keep P), scaled by rinv once at the end;
+// dS as in dQ (the dP accumulator starts at 0, -delta joins after the product).
+template <int D, bool CAUSAL, int NS, bool BND = false, bool DROP = false>
 __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
   static_assert(!(BND && CAUSAL), "BND: the causal bound is folded into khi / qlo");
   constexpr int DK = D / 16, DB = D / 32, TILE = KT * 2 * D, STG = 2 * TILE + 512;
@@ -512,6 +571,10 @@ __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
     const char* Qt = lds[it % NS];
     const char* Ot = Qt + TILE;  // dO
     const float* rs = reinterpret_cast<const float*>(Qt + 2 * TILE);
+    uint64_t colkey = 0;  // DROP: head key ^ the key's half of the hash counter
+    if constexpr (DROP)
+      colkey = dropout_head_key(a.drop_seed, kDropStreamAttn, b, hk * G + gs * gper + it / per) ^
+               (uint64_t)((uint32_t)key >> 2);
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
       if (BND ? (qs0 + 32 * qb + 32 <= rg.wlo || qs0 + 32 * qb >= rg.whi) : (CAUSAL && qs0 + 32 * qb + 31 < kw0)) continue;
@@ -521,7 +584,11 @@ __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
         const float4 nl = *reinterpret_cast<const float4*>(rs + 32 * qb + 8 * g + 4 * h);
         const float4 nd = *reinterpret_cast<const float4*>(rs + 64 + 32 * qb + 8 * g + 4 * h);
         s[4 * g] = nl.x; s[4 * g + 1] = nl.y; s[4 * g + 2] = nl.z; s[4 * g + 3] = nl.w;
-        dp[4 * g] = nd.x; dp[4 * g + 1] = nd.y; dp[4 * g + 2] = nd.z; dp[4 * g + 3] = nd.w;
+        if constexpr (DROP) {
+          dp[4 * g] = dp[4 * g + 1] = dp[4 * g + 2] = dp[4 * g + 3] = 0.f;
+        } else {
+          dp[4 * g] = nd.x; dp[4 * g + 1] = nd.y; dp[4 * g + 2] = nd.z; dp[4 * g + 3] = nd.w;
+        }
       }
 #pragma unroll
       for (int dk = 0; dk < DK; ++dk) s = MFMA32(row_frag<D>(Qt, 32 * qb, dk, lane), kf[dk], s);
@@ -538,7 +605,27 @@ __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
           p = 0.f;
         }
         s[r] = p;
-        dp[r] = p * dp[r];
+        if constexpr (!DROP) dp[r] = p * dp[r];
+      }
+      if constexpr (DROP) {
+        const int sh = 8 * (key & 3);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int qi0 = qs0 + 32 * qb + 8 * g + 4 * h;  // the group's 4 queries: two 2-row hash blocks
+          const float4 nd = *reinterpret_cast<const float4*>(rs + 64 + 32 * qb + 8 * g + 4 * h);
+          const float ndv[4] = {nd.x, nd.y, nd.z, nd.w};  // -delta of the 4 queries
+#pragma unroll
+          for (int j2 = 0; j2 < 2; ++j2) {
+            const uint64_t wd = splitmix64(colkey ^ ((uint64_t)((uint32_t)(qi0 + 2 * j2) >> 1) << 32));
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+              const int r = 4 * g + 2 * j2 + e;
+              const bool kp = (((uint32_t)(wd >> (32 * e)) >> sh) & 0xffu) >= a.drop_thr;
+              dp[r] = s[r] * (kp ? fmaf(dp[r], a.drop_rinv, ndv[2 * j2 + e]) : ndv[2 * j2 + e]);
+              if (!kp) s[r] = 0.f;
+            }
+          }
+        }
       }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
@@ -558,6 +645,12 @@ __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
   const bool kok = key < kv_end;
   auto keep = [kok](float x) { return kok ? x : 0.f; };
   const float sc = a.scale;
+  if constexpr (DROP) {
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dva[db][r] *= a.drop_rinv;
+  }
   if (a.gsplit == 1) {
     const int64_t off = b * a.gkb + (int64_t)key * a.gks + hk * a.gkh;
 #pragma unroll
@@ -589,21 +682,21 @@ __device__ __forceinline__ void attn_dkdv_body(const Args& a) {
 
 // Register budgets: the head-dim-64 backward kernels fit two waves per SIMD (<= 256 registers);
 // the head-dim-128 ones would spill there, so they keep one wave per SIMD and every register.
-template <int D, bool CAUSAL, int NS = 2, bool BND = false>
+template <int D, bool CAUSAL, int NS = 2, bool BND = false, bool DROP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_dq(Args a) {
-  attn_dq_body<D, CAUSAL, NS, BND>(a);
+  attn_dq_body<D, CAUSAL, NS, BND, DROP>(a);
 }
-template <int D, bool CAUSAL, int NS = 2, bool BND = false>
+template <int D, bool CAUSAL, int NS = 2, bool BND = false, bool DROP = false>
 __global__ __launch_bounds__(256) void k_attn_dq_wide(Args a) {
-  attn_dq_body<D, CAUSAL, NS, BND>(a);
+  attn_dq_body<D, CAUSAL, NS, BND, DROP>(a);
 }
-template <int D, bool CAUSAL, int NS = 2, bool BND = false>
+template <int D, bool CAUSAL, int NS = 2, bool BND = false, bool DROP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_attn_dkdv(Args a) {
-  attn_dkdv_body<D, CAUSAL, NS, BND>(a);
+  attn_dkdv_body<D, CAUSAL, NS, BND, DROP>(a);
 }
-template <int D, bool CAUSAL, int NS = 2, bool BND = false>
+template <int D, bool CAUSAL, int NS = 2, bool BND = false, bool DROP = false>
 __global__ __launch_bounds__(256) void k_attn_dkdv_wide(Args a) {
-  attn_dkdv_body<D, CAUSAL, NS, BND>(a);
+  attn_dkdv_body<D, CAUSAL, NS, BND, DROP>(a);
 }
 
 // dK / dV of a split GQA group: sum the slices in order (deterministic), cast to bf16 into the
@@ -737,16 +830,56 @@ int attn_stages(bool causal, bool backward) {
   } while (0)
 #define ATTN_DISPATCH(KER, D_, CAUSAL_, BND_, GRID, A) ATTN_DISPATCH2(KER, KER, D_, CAUSAL_, false, BND_, GRID, A)
 
+// the DROP forms: two LDS stages only (HIPPS_ATTN_STAGES=3 with dropout runs these)
+#define ATTN_DISPATCH_DROP(KER64, KER128, D_, CAUSAL_, BND_, GRID, A)                                  \
+  do {                                                                                                 \
+    auto st = c10::hip::getCurrentHIPStream();                                                         \
+    if ((D_) == 64) {                                                                                  \
+      if (BND_) hipLaunchKernelGGL((KER64<64, false, 2, true, true>), dim3(GRID), dim3(256), 0, st, A); \
+      else if (CAUSAL_) hipLaunchKernelGGL((KER64<64, true, 2, false, true>), dim3(GRID), dim3(256), 0, st, A); \
+      else hipLaunchKernelGGL((KER64<64, false, 2, false, true>), dim3(GRID), dim3(256), 0, st, A);     \
+    } else {                                                                                           \
+      if (BND_) hipLaunchKernelGGL((KER128<128, false, 2, true, true>), dim3(GRID), dim3(256), 0, st, A); \
+      else if (CAUSAL_) hipLaunchKernelGGL((KER128<128, true, 2, false, true>), dim3(GRID), dim3(256), 0, st, A); \
+      else hipLaunchKernelGGL((KER128<128, false, 2, false, true>), dim3(GRID), dim3(256), 0, st, A);   \
+    }                                                                                                  \
+  } while (0)
+
+// dropout_p -> Args: thr = round(256 p) (at most 255), rinv = 256 / (256 - thr); reference.py
+// dropout_params is the twin.  Returns whether the DROP kernels run (thr > 0).
+bool set_dropout(Args& a, double p, uint64_t seed) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "attn: dropout_p must be in [0, 1), got ", p);
+  const uint32_t thr = std::min<uint32_t>(255u, (uint32_t)std::floor(p * 256.0 + 0.5));
+  TORCH_CHECK(thr == 0 || a.Hq < (1 << 24), "attn: dropout needs fewer than 2^24 query heads");
+  a.drop_seed = seed;
+  a.drop_thr = thr;
+  a.drop_rinv = 256.0f / (float)(256u - thr);
+  return thr > 0;
+}
+
+// the device mask function at arbitrary indices (tests: the twin of reference.dropout_keep)
+__global__ __launch_bounds__(256) void k_dropout_keep(uint64_t seed, uint32_t thr, int64_t n,
+                                                      const int64_t* __restrict__ b, const int64_t* __restrict__ hq,
+                                                      const int64_t* __restrict__ qi, const int64_t* __restrict__ ki,
+                                                      uint8_t* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    out[i] = dropout_keep(seed, kDropStreamAttn, (uint32_t)b[i], (uint32_t)hq[i], (uint32_t)qi[i], (uint32_t)ki[i], thr)
+                 ? 1 : 0;
+}
+
 }  // namespace attn
 
 // o = softmax(q k^T * scale + mask) v  for q [B, Sq, Hq, D], k / v [B, Sk, Hkv, D] (bf16);
 // returns (o [B, Sq, Hq, D] contiguous, lse [B, Hq, Sq] f32 natural log).  klo / khi (both or
 // neither; int32 [B or 1, S]): query i sees only keys [klo[i], khi[i]), ANDed with kv_len; the
-// causal bound must already be in khi (``causal`` then only orders the launch)
+// causal bound must already be in khi (``causal`` then only orders the launch).  dropout_p > 0:
+// attention-probability dropout with the counter-based mask of (dropout_seed, b, hq, i, j)
+// (common.h dropout_keep); a p that rounds to threshold 0 runs the plain kernels
 std::vector<at::Tensor> attn_forward(at::Tensor q, at::Tensor k, at::Tensor v, bool causal, double scale,
                                      c10::optional<at::Tensor> kvlen, c10::optional<at::Tensor> klo,
-                                     c10::optional<at::Tensor> khi) {
+                                     c10::optional<at::Tensor> khi, double dropout_p, uint64_t dropout_seed) {
   attn::Args a = attn::make_args(q, k, v, causal, scale, kvlen);
+  const bool drop = attn::set_dropout(a, dropout_p, dropout_seed);
   const bool bnd = attn::given(klo) || attn::given(khi);
   if (bnd) {
     TORCH_CHECK(attn::given(klo) && attn::given(khi), "attn: klo and khi come together");
@@ -763,18 +896,21 @@ std::vector<at::Tensor> attn_forward(at::Tensor q, at::Tensor k, at::Tensor v, b
   a.nblk = a.nqblk = (a.Sq + attn::QB - 1) / attn::QB;
   const int64_t grid = (int64_t)a.nblk * a.B * a.Hq;
   TORCH_CHECK(grid < (int64_t(1) << 31), "attn: grid");
-  ATTN_DISPATCH(attn::k_attn_fwd, D, causal, bnd, (unsigned)grid, a);
+  if (drop) ATTN_DISPATCH_DROP(attn::k_attn_fwd, attn::k_attn_fwd, D, causal, bnd, (unsigned)grid, a);
+  else ATTN_DISPATCH(attn::k_attn_fwd, D, causal, bnd, (unsigned)grid, a);
   return {o, lse};
 }
 
 // gradients of attn_forward: returns (dq, dk, dv) contiguous in the layouts of q, k, v
+// (dropout_p / dropout_seed: those of the forward -- the mask is regenerated, not stored)
 std::vector<at::Tensor> attn_backward(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                       at::Tensor lse, bool causal, double scale, c10::optional<at::Tensor> kvlen,
                                       c10::optional<at::Tensor> dq_out, c10::optional<at::Tensor> dk_out,
                                       c10::optional<at::Tensor> dv_out, c10::optional<at::Tensor> klo,
                                       c10::optional<at::Tensor> khi, c10::optional<at::Tensor> qlo,
-                                      c10::optional<at::Tensor> qhi) {
+                                      c10::optional<at::Tensor> qhi, double dropout_p, uint64_t dropout_seed) {
   attn::Args a = attn::make_args(q, k, v, causal, scale, kvlen);
+  const bool drop = attn::set_dropout(a, dropout_p, dropout_seed);
   // the row ranges the forward ran with, and their transpose (key j is seen by queries [qlo[j], qhi[j]))
   const bool bnd = attn::given(klo) || attn::given(khi) || attn::given(qlo) || attn::given(qhi);
   if (bnd) {
@@ -820,7 +956,8 @@ std::vector<at::Tensor> attn_backward(at::Tensor dout, at::Tensor q, at::Tensor 
   at::Tensor rowstat = at::empty({(int64_t)a.B * a.Hq * 2 * a.nblk * 128}, q.options().dtype(at::kFloat));
   a.rowstat = rowstat.data_ptr<float>();
   const int64_t gq = (int64_t)a.nblk * a.B * a.Hq;
-  ATTN_DISPATCH2(attn::k_attn_dq, attn::k_attn_dq_wide, D, causal, true, bnd, (unsigned)gq, a);
+  if (drop) ATTN_DISPATCH_DROP(attn::k_attn_dq, attn::k_attn_dq_wide, D, causal, bnd, (unsigned)gq, a);
+  else ATTN_DISPATCH2(attn::k_attn_dq, attn::k_attn_dq_wide, D, causal, true, bnd, (unsigned)gq, a);
   // dK / dV: split the GQA group over workgroups when the (batch, kv head, key block) grid is
   // small: under the causal mask the first key block of a sequence sweeps every query tile and
   // the last one a single tile, so a grid that fits the GPU in one wave runs as long as its
@@ -839,7 +976,8 @@ std::vector<at::Tensor> attn_backward(at::Tensor dout, at::Tensor q, at::Tensor 
   }
   a.nblk = nkb;
   const int64_t gk = (int64_t)nkb * a.B * a.Hkv * gsplit;
-  ATTN_DISPATCH2(attn::k_attn_dkdv, attn::k_attn_dkdv_wide, D, causal, true, bnd, (unsigned)gk, a);
+  if (drop) ATTN_DISPATCH_DROP(attn::k_attn_dkdv, attn::k_attn_dkdv_wide, D, causal, bnd, (unsigned)gk, a);
+  else ATTN_DISPATCH2(attn::k_attn_dkdv, attn::k_attn_dkdv_wide, D, causal, true, bnd, (unsigned)gk, a);
   if (gsplit > 1) {
     const int64_t n = dk.numel();
     const int grid = (int)std::min<int64_t>(2048, (2 * n / 4 + 255) / 256);
@@ -847,6 +985,23 @@ std::vector<at::Tensor> attn_backward(at::Tensor dout, at::Tensor q, at::Tensor 
                        a.Hkv, a.Sk, a.gkb, a.gks, a.gkh, (uint16_t*)dk.data_ptr(), (uint16_t*)dv.data_ptr());
   }
   return {dq, dk, dv};
+}
+
+// uint8 [n]: dropout_keep(seed, b[i], hq[i], qi[i], ki[i]) of the attention kernels at dropout_p,
+// for int64 index tensors on the device (b < 2^32, hq < 2^24, qi / ki < 2^24)
+at::Tensor attn_dropout_keep(uint64_t seed, double p, at::Tensor b, at::Tensor hq, at::Tensor qi, at::Tensor ki) {
+  attn::Args a{};
+  attn::set_dropout(a, p, seed);
+  const int64_t n = b.numel();
+  for (const at::Tensor* t : {&b, &hq, &qi, &ki})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kLong && t->is_contiguous() && t->numel() == n &&
+                    t->device() == b.device(), "attn_dropout_keep: int64 contiguous device tensors of one length");
+  at::Tensor out = at::empty({n}, b.options().dtype(at::kByte));
+  if (n > 0)
+    hipLaunchKernelGGL(attn::k_dropout_keep, grid_for(n), 256, 0, c10::hip::getCurrentHIPStream(), seed, a.drop_thr,
+                       n, b.data_ptr<int64_t>(), hq.data_ptr<int64_t>(), qi.data_ptr<int64_t>(),
+                       ki.data_ptr<int64_t>(), out.data_ptr<uint8_t>());
+  return out;
 }
 
 }  // namespace hipps

@@ -108,13 +108,14 @@ void colsum_fold(at::Tensor part, at::Tensor out);
 void colsum_bf16(at::Tensor x, at::Tensor out);
 std::vector<at::Tensor> attn_forward(at::Tensor q, at::Tensor k, at::Tensor v, bool causal, double scale,
                                      c10::optional<at::Tensor> kvlen, c10::optional<at::Tensor> klo,
-                                     c10::optional<at::Tensor> khi);
+                                     c10::optional<at::Tensor> khi, double dropout_p, uint64_t dropout_seed);
+at::Tensor attn_dropout_keep(uint64_t seed, double p, at::Tensor b, at::Tensor hq, at::Tensor qi, at::Tensor ki);
 std::vector<at::Tensor> attn_backward(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                                       at::Tensor lse, bool causal, double scale, c10::optional<at::Tensor> kvlen,
                                       c10::optional<at::Tensor> dq_out, c10::optional<at::Tensor> dk_out,
                                       c10::optional<at::Tensor> dv_out, c10::optional<at::Tensor> klo,
                                       c10::optional<at::Tensor> khi, c10::optional<at::Tensor> qlo,
-                                      c10::optional<at::Tensor> qhi);
+                                      c10::optional<at::Tensor> qhi, double dropout_p, uint64_t dropout_seed);
 void swiglu_forward(at::Tensor a, at::Tensor b, at::Tensor c);
 void ln_forward(at::Tensor x, at::Tensor w, at::Tensor b, at::Tensor y, at::Tensor mean, at::Tensor rstd, double eps);
 void ln_backward(at::Tensor dy, at::Tensor x, at::Tensor mean, at::Tensor rstd, at::Tensor w, at::Tensor dx,
@@ -310,14 +311,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("colsum_bf16", &hipps::colsum_bf16, "fp32 column sums of a bf16 [rows, cols] matrix (bias gradients)");
   m.def("attn_forward", &hipps::attn_forward, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
         py::arg("scale"), py::arg("kv_len") = py::none(), py::arg("klo") = py::none(), py::arg("khi") = py::none(),
+        py::arg("dropout_p") = 0.0, py::arg("dropout_seed") = (uint64_t)0,
         "flash attention forward on MFMA: q [B,Sq,Hq,D], k/v [B,Sk,Hkv,D] bf16 -> (o, lse); klo / khi int32 "
-        "[B or 1, S]: query i sees keys [klo[i], khi[i]) (attn.hip)");
+        "[B or 1, S]: query i sees keys [klo[i], khi[i]); dropout_p in [0, 1) with a 64-bit dropout_seed: "
+        "attention-probability dropout by a counter-based mask (attn.hip)");
+  m.def("attn_dropout_keep", &hipps::attn_dropout_keep, py::arg("seed"), py::arg("p"), py::arg("b"), py::arg("hq"),
+        py::arg("qi"), py::arg("ki"),
+        "uint8 [n]: whether the attention kernels keep P[b, hq, qi, ki] at (seed, p); int64 device index tensors");
   m.def("attn_backward", &hipps::attn_backward, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o"), py::arg("lse"), py::arg("causal"), py::arg("scale"), py::arg("kv_len") = py::none(),
         py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(), py::arg("dv_out") = py::none(),
         py::arg("klo") = py::none(), py::arg("khi") = py::none(), py::arg("qlo") = py::none(),
-        py::arg("qhi") = py::none(),
-        "flash attention backward (deterministic dQ and dK/dV kernels) -> (dq, dk, dv) (attn.hip)");
+        py::arg("qhi") = py::none(), py::arg("dropout_p") = 0.0, py::arg("dropout_seed") = (uint64_t)0,
+        "flash attention backward (deterministic dQ and dK/dV kernels) -> (dq, dk, dv); dropout_p / "
+        "dropout_seed as in the forward (attn.hip)");
   m.def("xent_forward", &hipps::xent_forward,
         "fused softmax cross-entropy over bf16 logits: (mean loss, counted rows, per-row log-sum-exp)");
   m.def("xent_backward", &hipps::xent_backward, py::arg("logits"), py::arg("labels"), py::arg("lse"), py::arg("gout"),

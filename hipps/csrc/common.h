@@ -96,6 +96,33 @@ __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t idx) {
   return (float)(splitmix64(seed ^ (idx * 0xD1B54A32D192ED03ull)) >> 40) * (1.0f / 16777216.0f);
 }
 
+// ---- dropout mask: keep(seed, stream, b, h, i, j), a pure function of its arguments --------
+// (reference.py dropout_keep is the numpy twin, bit for bit.)  One 64-bit hash covers a block of
+// 2 rows x 4 columns as eight 8-bit fields: element (i, j) reads byte 4 (i & 1) + (j & 3) of
+//   dropout_word(dropout_head_key(seed, stream, b, h), i, j)
+// and is kept iff that byte >= thr, thr = round(256 p) -- so the drop probability is thr / 256.
+// A lane that holds 4 consecutive columns of one row (attention forward / dQ) pays one hash for
+// them, one that holds 4 consecutive rows of one column (dK/dV) two.  b < 2^32, h < 2^24, stream
+// < 2^8 and i, j < 2^25 occupy disjoint bits of the two hash inputs: no aliasing.
+constexpr uint64_t kDropStreamAttn = 1;  // attention probabilities (other dropout sites: other ids)
+__device__ __forceinline__ uint64_t dropout_head_key(uint64_t seed, uint64_t stream, uint32_t b, uint32_t h) {
+  return splitmix64(splitmix64(seed) ^ ((stream << 56) | ((uint64_t)b << 24) | (uint64_t)h));
+}
+__device__ __forceinline__ uint64_t dropout_word(uint64_t head_key, uint32_t i, uint32_t j) {
+  return splitmix64(head_key ^ (((uint64_t)(i >> 1) << 32) | (uint64_t)(j >> 2)));
+}
+// the 4 fields of row i (columns 4 (j >> 2) .. + 3, column c in byte c) out of the block's word
+__device__ __forceinline__ uint32_t dropout_row4(uint64_t word, uint32_t i) {
+  return (i & 1) ? (uint32_t)(word >> 32) : (uint32_t)word;
+}
+__device__ __forceinline__ bool dropout_keep4(uint32_t row4, int c, uint32_t thr) {
+  return ((row4 >> (8 * c)) & 0xffu) >= thr;
+}
+__device__ __forceinline__ bool dropout_keep(uint64_t seed, uint64_t stream, uint32_t b, uint32_t h, uint32_t i,
+                                             uint32_t j, uint32_t thr) {
+  return dropout_keep4(dropout_row4(dropout_word(dropout_head_key(seed, stream, b, h), i, j), i), j & 3, thr);
+}
+
 // ---- wave-level reductions (64 lanes) ------------------------------------------------------
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll

@@ -12,7 +12,8 @@
 
 Attention is ``hipps.ops.nn.attention`` (csrc/attn.hip: MFMA flash attention, forward and a
 deterministic backward, causal + grouped-query heads for Llama, key padding for BERT, packed
-documents (``doc_ids``) for both and a sliding window (``LlamaConfig.window``)) on the
+documents (``doc_ids``) for both, a sliding window (``LlamaConfig.window``) and in-kernel dropout of
+the attention probabilities in training (``attn_dropout`` of either config)) on the
 [B, S, H, hd] views of the projection outputs (no transposes); the
 projections and MLPs are ``hipps.ops.nn.Linear`` (per shape hipBLASLt or the hipps gemm2 cores,
 reading the engine's bf16 weight shadow, fp32 weight gradients written directly, the residual add
@@ -58,12 +59,14 @@ class BertConfig:
     max_pos: int = 512
     type_vocab: int = 2
     eps: float = 1e-12
+    attn_dropout: float = 0.0  # dropout of the attention probabilities, in training (BertModel: 0.1)
 
 
 class BertLayer(nn.Module):
     def __init__(self, c: BertConfig):
         super().__init__()
         self.heads = c.heads
+        self.attn_dropout = c.attn_dropout
         # the query / key / value projections as ONE [3 * hidden, hidden] weight (+ [3 * hidden]
         # bias): same parameters and math as three Linears, one GEMM each way instead of three,
         # and the input gradient comes out of one GEMM (no two autograd adds per layer)
@@ -80,6 +83,7 @@ class BertLayer(nn.Module):
     def forward(self, x, mask=None, bounds=None):
         B, S, D = x.shape
         h = self.heads
+        pdrop = self.attn_dropout if self.training else 0.0
 
         link = hnn.ResidualLink()  # x's gradient from attn_out's residual joins qkv's input-gradient GEMM
         qkv = self.qkv(x, link=link).view(B, S, 3, h, D // h)
@@ -87,13 +91,13 @@ class BertLayer(nn.Module):
             # the packed [B, S, 3, H, hd] projection straight into the hipps flash-attention
             # kernels (csrc/attn.hip); ``mask`` may be the int32 [B] key lengths of a padded batch
             # (``bounds``: the packed-document mask, hnn.attention_bounds)
-            a = hnn.attention_qkv(qkv, kv_len=mask, bounds=bounds)
+            a = hnn.attention_qkv(qkv, kv_len=mask, bounds=bounds, dropout_p=pdrop)
         else:
             if bounds is not None:  # the documents join the SDPA mask
                 dense = bounds.dense_mask(x.device)[:, None]
                 mask = mask & dense if mask.dtype == torch.bool else mask.masked_fill(~dense, -math.inf)
             q, k, v = (t.transpose(1, 2) for t in qkv.unbind(2))
-            a = F.scaled_dot_product_attention(q, k, v, attn_mask=mask).transpose(1, 2)
+            a = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=pdrop).transpose(1, 2)
         a = a.reshape(B, S, D)
         # residual adds ride in the output projections (GEMM epilogue / hipBLASLt C)
         # (colsum_dx: the LayerNorm backward also sums its dx -- attn_out's / out's bias gradient)
@@ -170,6 +174,7 @@ class LlamaConfig:
     theta: float = 500000.0
     max_seq: int = 8192
     window: int = 0  # sliding attention window (the last ``window`` keys, the query included); 0: none
+    attn_dropout: float = 0.0  # dropout of the attention probabilities, in training
 
 
 class RMSNorm(nn.Module):
@@ -233,6 +238,7 @@ class LlamaBlock(nn.Module):
         B, S, D = x.shape
         c = self.c
         hd = D // c.heads
+        pdrop = c.attn_dropout if self.training else 0.0
         if y is None:
             h = self.attn_norm(x)
         else:
@@ -240,12 +246,12 @@ class LlamaBlock(nn.Module):
         y = self.wqkv(h)  # [B, S, (heads + 2 kv_heads) * hd]
         if hnn.rope_attention_packed_ok(y, cos, c.heads, c.kv_heads):
             # RoPE + causal GQA flash attention on the packed projection (csrc/act.hip, attn.hip)
-            a = hnn.rope_attention_packed(y, cos, sin, c.heads, c.kv_heads, bounds=bounds)
+            a = hnn.rope_attention_packed(y, cos, sin, c.heads, c.kv_heads, bounds=bounds, dropout_p=pdrop)
         else:
             q, k, v = y.split([c.heads * hd, c.kv_heads * hd, c.kv_heads * hd], dim=-1)
             q = _rope(q.reshape(B, S, c.heads, hd).contiguous(), cos, sin)
             k = _rope(k.reshape(B, S, c.kv_heads, hd).contiguous(), cos, sin)
-            a = hnn.attention(q, k, v.reshape(B, S, c.kv_heads, hd), causal=True, bounds=bounds)
+            a = hnn.attention(q, k, v.reshape(B, S, c.kv_heads, hd), causal=True, bounds=bounds, dropout_p=pdrop)
         x, h = self.ffn_norm(x, add=self.wo(a.reshape(B, S, D)))
         return x, self.w2(hnn.swiglu_packed(self.w13(h)))
 

@@ -1254,17 +1254,84 @@ def attention_ok(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool
             and 0 < q.shape[1] < (1 << 24) and 0 < k.shape[1] < (1 << 24))
 
 
+# ---- attention dropout: the seed of each call's counter-based mask ----------------------------
+# The kernels regenerate the mask of a call from one 64-bit seed (csrc/common.h dropout_keep,
+# reference.dropout_keep), so "the generator" is a process-wide (base, counter) pair: every call
+# with dropout_p > 0 and no explicit seed takes next_dropout_seed().  Equal state and call order
+# give equal masks; the base mixes the distributed rank in, so ranks seeded alike still differ.
+_M64 = (1 << 64) - 1
+_DROPOUT_RNG = {"base": None, "counter": 0}
+
+
+def _mix64(x: int) -> int:  # splitmix64 on Python ints
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def _dropout_rank() -> int:
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank()
+    return int(_os.environ.get("RANK", "0") or 0)
+
+
+def manual_dropout_seed(seed: int) -> None:
+    """Restart the dropout seed sequence of this process from ``seed`` (the rank is mixed in)."""
+    _DROPOUT_RNG["base"] = _mix64((int(seed) & _M64) ^ _mix64(_dropout_rank() + 1))
+    _DROPOUT_RNG["counter"] = 0
+
+
+def next_dropout_seed() -> int:
+    """The seed of the next dropout mask: a hash of (base, counter), counter += 1.  The base comes
+    from ``torch.initial_seed()`` and the distributed rank at first use (or manual_dropout_seed)."""
+    if _DROPOUT_RNG["base"] is None:
+        manual_dropout_seed(torch.initial_seed())
+    c = _DROPOUT_RNG["counter"]
+    _DROPOUT_RNG["counter"] = c + 1
+    return _mix64(_DROPOUT_RNG["base"] ^ _mix64(c))
+
+
+def dropout_rng_state():
+    """(base, counter) of the dropout seed sequence, for :func:`set_dropout_rng_state`."""
+    if _DROPOUT_RNG["base"] is None:
+        manual_dropout_seed(torch.initial_seed())
+    return (_DROPOUT_RNG["base"], _DROPOUT_RNG["counter"])
+
+
+def set_dropout_rng_state(state) -> None:
+    base, counter = state
+    _DROPOUT_RNG["base"], _DROPOUT_RNG["counter"] = int(base) & _M64, int(counter)
+
+
+def _dropout_args(dropout_p: float, dropout_seed: Optional[int], kernel: bool):
+    """(p, seed) of a call: p checked (ValueError outside [0, 1)); p == 0 -> (0.0, 0).  On the
+    kernel route a call without a seed draws one from next_dropout_seed()."""
+    p = float(dropout_p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"attention: dropout_p must be in [0, 1), got {dropout_p}")
+    if p == 0.0:
+        return 0.0, 0
+    if dropout_seed is not None:
+        return p, int(dropout_seed) & _M64
+    return p, (next_dropout_seed() if kernel else 0)
+
+
 class _FlashAttention(torch.autograd.Function):
     """o = softmax(q k^T * scale [+ causal / key-padding mask]) v on [B, S, H, D] bf16 operands
     (csrc/attn.hip): forward keeps only o and the per-row log-sum-exp; backward recomputes P in
     the dQ and the dK/dV kernels (deterministic: no float atomics)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale, kv_len, bounds=None):
+    def forward(ctx, q, k, v, causal, scale, kv_len, bounds=None, drop=None):
         r = (None,) * 4 if bounds is None else tuple(bounds[:4])  # klo, khi, qlo, qhi
-        o, lse = native().attn_forward(q, k, v, causal, scale, kv_len, r[0], r[1])
+        if drop is None:
+            o, lse = native().attn_forward(q, k, v, causal, scale, kv_len, r[0], r[1])
+        else:  # (dropout_p, dropout_seed): the backward regenerates the same mask
+            o, lse = native().attn_forward(q, k, v, causal, scale, kv_len, r[0], r[1], drop[0], drop[1])
         ctx.save_for_backward(q, k, v, o, lse, kv_len, *r)
-        ctx.causal, ctx.scale = causal, scale
+        ctx.causal, ctx.scale, ctx.drop = causal, scale, drop
         return o
 
     @staticmethod
@@ -1273,8 +1340,9 @@ class _FlashAttention(torch.autograd.Function):
         do = do.to(torch.bfloat16)
         if not _attn_rows_ok(do):
             do = do.contiguous()
-        dq, dk, dv = native().attn_backward(do, q, k, v, o, lse, ctx.causal, ctx.scale, kv_len, None, None, None, *r)
-        return dq, dk, dv, None, None, None, None
+        dq, dk, dv = native().attn_backward(do, q, k, v, o, lse, ctx.causal, ctx.scale, kv_len, None, None, None, *r,
+                                            *(ctx.drop or ()))
+        return dq, dk, dv, None, None, None, None, None
 
 
 class _FlashAttentionQKV(torch.autograd.Function):
@@ -1285,12 +1353,15 @@ class _FlashAttentionQKV(torch.autograd.Function):
     three separate views."""
 
     @staticmethod
-    def forward(ctx, qkv, causal, scale, kv_len, bounds=None):
+    def forward(ctx, qkv, causal, scale, kv_len, bounds=None, drop=None):
         q, k, v = qkv.unbind(2)
         r = (None,) * 4 if bounds is None else tuple(bounds[:4])
-        o, lse = native().attn_forward(q, k, v, causal, scale, kv_len, r[0], r[1])
+        if drop is None:
+            o, lse = native().attn_forward(q, k, v, causal, scale, kv_len, r[0], r[1])
+        else:
+            o, lse = native().attn_forward(q, k, v, causal, scale, kv_len, r[0], r[1], drop[0], drop[1])
         ctx.save_for_backward(qkv, o, lse, kv_len, *r)
-        ctx.causal, ctx.scale = causal, scale
+        ctx.causal, ctx.scale, ctx.drop = causal, scale, drop
         return o
 
     @staticmethod
@@ -1302,12 +1373,13 @@ class _FlashAttentionQKV(torch.autograd.Function):
         g = torch.empty(qkv.shape, dtype=torch.bfloat16, device=qkv.device)
         q, k, v = qkv.unbind(2)
         gq, gk, gv = g.unbind(2)
-        native().attn_backward(do, q, k, v, o, lse, ctx.causal, ctx.scale, kv_len, gq, gk, gv, *r)
-        return g, None, None, None, None
+        native().attn_backward(do, q, k, v, o, lse, ctx.causal, ctx.scale, kv_len, gq, gk, gv, *r, *(ctx.drop or ()))
+        return g, None, None, None, None, None
 
 
 def attention_qkv(qkv: torch.Tensor, causal: bool = False, scale: Optional[float] = None,
-                  kv_len: Optional[torch.Tensor] = None, bounds: Optional[AttnBounds] = None) -> torch.Tensor:
+                  kv_len: Optional[torch.Tensor] = None, bounds: Optional[AttnBounds] = None,
+                  dropout_p: float = 0.0, dropout_seed: Optional[int] = None) -> torch.Tensor:
     """:func:`attention` of q, k, v packed as ``qkv`` [B, S, 3, H, D] (e.g. ``linear(x, W_qkv)
     .view(B, S, 3, H, D)``); returns [B, S, H, D]."""
     q, k, v = qkv.unbind(2)
@@ -1315,10 +1387,14 @@ def attention_qkv(qkv: torch.Tensor, causal: bool = False, scale: Optional[float
     if attention_ok(q, k, v, causal, bounds) and qkv.dtype == torch.bfloat16:
         sc = float(scale) if scale is not None else 1.0 / (qkv.shape[-1] ** 0.5)
         kl = None if kv_len is None else kv_len.to(device=qkv.device, dtype=torch.int32).contiguous()
+        drop = _dropout_args(dropout_p, dropout_seed, True)
+        if drop[0] > 0.0:
+            return _FlashAttentionQKV.apply(qkv, bool(causal), sc, kl, bounds, drop)
         if bounds is None:
             return _FlashAttentionQKV.apply(qkv, bool(causal), sc, kl)
         return _FlashAttentionQKV.apply(qkv, bool(causal), sc, kl, bounds)
-    return attention(q, k, v, causal=causal, scale=scale, kv_len=kv_len, bounds=bounds)
+    return attention(q, k, v, causal=causal, scale=scale, kv_len=kv_len, bounds=bounds, dropout_p=dropout_p,
+                     dropout_seed=dropout_seed)
 
 
 class _RopeAttentionPacked(torch.autograd.Function):
@@ -1330,7 +1406,7 @@ class _RopeAttentionPacked(torch.autograd.Function):
     three views of y."""
 
     @staticmethod
-    def forward(ctx, y, cos, sin, hq, hkv, causal, scale, bounds=None):
+    def forward(ctx, y, cos, sin, hq, hkv, causal, scale, bounds=None, drop=None):
         B, S, W = y.shape
         D = W // (hq + 2 * hkv)
         y2 = y.view(B * S, W)
@@ -1341,9 +1417,13 @@ class _RopeAttentionPacked(torch.autograd.Function):
         C.rope_apply(y2[:, hq * D:(hq + hkv) * D], k.view(B * S, hkv * D), cos, sin, S, D, 1.0)
         v = y[:, :, (hq + hkv) * D:].view(B, S, hkv, D)
         r = (None,) * 4 if bounds is None else tuple(bounds[:4])
-        o, lse = C.attn_forward(q, k, v, causal, scale, None, r[0], r[1])
+        if drop is None:
+            o, lse = C.attn_forward(q, k, v, causal, scale, None, r[0], r[1])
+        else:
+            o, lse = C.attn_forward(q, k, v, causal, scale, None, r[0], r[1], drop[0], drop[1])
         ctx.save_for_backward(q, k, y, o, lse, cos, sin, *r)
         ctx.meta = (hq, hkv, D, causal, scale)
+        ctx.drop = drop
         return o
 
     @staticmethod
@@ -1360,11 +1440,11 @@ class _RopeAttentionPacked(torch.autograd.Function):
         gk = g[:, :, hq * D:(hq + hkv) * D].view(B, S, hkv, D)
         gv = g[:, :, (hq + hkv) * D:].view(B, S, hkv, D)
         C = native()
-        C.attn_backward(do, q, k, v, o, lse, causal, scale, None, gq, gk, gv, *r)
+        C.attn_backward(do, q, k, v, o, lse, causal, scale, None, gq, gk, gv, *r, *(ctx.drop or ()))
         g2 = g.view(B * S, W)
         for a, b in ((0, hq * D), (hq * D, (hq + hkv) * D)):  # rotate back in place (the backward of RoPE)
             C.rope_apply(g2[:, a:b], g2[:, a:b], cos, sin, S, D, -1.0)
-        return g, None, None, None, None, None, None, None
+        return g, None, None, None, None, None, None, None, None
 
 
 def rope_attention_packed_ok(y: torch.Tensor, cos: torch.Tensor, hq: int, hkv: int) -> bool:
@@ -1379,13 +1459,18 @@ def rope_attention_packed_ok(y: torch.Tensor, cos: torch.Tensor, hq: int, hkv: i
 
 def rope_attention_packed(y: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, hq: int, hkv: int,
                           causal: bool = True, scale: Optional[float] = None,
-                          bounds: Optional[AttnBounds] = None) -> torch.Tensor:
+                          bounds: Optional[AttnBounds] = None, dropout_p: float = 0.0,
+                          dropout_seed: Optional[int] = None) -> torch.Tensor:
     """Rotary embedding + (causal, grouped-query) attention of a packed q | k | v projection
     y [B, S, (hq + 2 hkv) * D]; returns [B, S, hq, D].  Callers check rope_attention_packed_ok.
-    ``bounds``: :func:`attention_bounds` (RoPE is relative: no position reset per document)."""
+    ``bounds``: :func:`attention_bounds` (RoPE is relative: no position reset per document).
+    ``dropout_p`` / ``dropout_seed``: as in :func:`attention`."""
     D = y.shape[-1] // (hq + 2 * hkv)
     sc = float(scale) if scale is not None else 1.0 / (D ** 0.5)
     bounds = _attn_bounds_for(bounds, y, y.shape[1], causal)
+    drop = _dropout_args(dropout_p, dropout_seed, True)
+    if drop[0] > 0.0:
+        return _RopeAttentionPacked.apply(y, cos, sin, int(hq), int(hkv), bool(causal), sc, bounds, drop)
     if bounds is None:
         return _RopeAttentionPacked.apply(y, cos, sin, int(hq), int(hkv), bool(causal), sc)
     return _RopeAttentionPacked.apply(y, cos, sin, int(hq), int(hkv), bool(causal), sc, bounds)
@@ -1393,7 +1478,8 @@ def rope_attention_packed(y: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = False,
               scale: Optional[float] = None, kv_len: Optional[torch.Tensor] = None,
-              bounds: Optional[AttnBounds] = None) -> torch.Tensor:
+              bounds: Optional[AttnBounds] = None, dropout_p: float = 0.0,
+              dropout_seed: Optional[int] = None) -> torch.Tensor:
     """Scaled dot-product attention on the [batch, seq, heads, head_dim] layout (the projection
     outputs viewed per head, no transposes): q [B, Sq, Hq, D], k / v [B, Sk, Hkv, D] with Hq a
     multiple of Hkv (grouped-query attention), optional causal mask (Sq == Sk) and key padding
@@ -1402,9 +1488,16 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = 
     with the others; a query row left with no key gives o = 0 and no gradient.  Returns
     [B, Sq, Hq, D].
 
+    ``dropout_p`` in [0, 1) drops attention probabilities (the rest scaled by 1 / (1 - p)); callers
+    pass it only in training.  On the kernels the mask is a counter-based function of
+    (seed, batch row, query head, query, key) that the backward regenerates; p is quantised to
+    round(256 p) / 256 (``reference.dropout_params``).  ``dropout_seed``: an explicit 64-bit seed,
+    else :func:`next_dropout_seed` (see :func:`manual_dropout_seed`, :func:`dropout_rng_state`).
+
     bf16 device operands with head dim 64 / 128 run the hipps flash-attention kernels (which skip
     the key tiles outside a row's document / window); anything else runs
-    ``F.scaled_dot_product_attention`` on the transposed views."""
+    ``F.scaled_dot_product_attention`` on the transposed views -- whose dropout draws from torch's
+    generator: another mask than the kernels', exact p, and ``dropout_seed`` is ignored."""
     D = q.shape[-1]
     sc = float(scale) if scale is not None else 1.0 / (D ** 0.5)
     bounds = _attn_bounds_for(bounds, q, k.shape[1], causal)
@@ -1412,9 +1505,13 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = 
         kl = None
         if kv_len is not None:
             kl = kv_len.to(device=q.device, dtype=torch.int32).contiguous()
+        drop = _dropout_args(dropout_p, dropout_seed, True)
+        if drop[0] > 0.0:
+            return _FlashAttention.apply(q, k, v, bool(causal), sc, kl, bounds, drop)
         if bounds is None:
             return _FlashAttention.apply(q, k, v, bool(causal), sc, kl)
         return _FlashAttention.apply(q, k, v, bool(causal), sc, kl, bounds)
+    dp = _dropout_args(dropout_p, dropout_seed, False)[0]
     qt, kt, vt = (t.transpose(1, 2) for t in (q, k, v))
     if k.shape[2] != q.shape[2]:
         rep = q.shape[2] // k.shape[2]
@@ -1429,7 +1526,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = 
         mask = mask[:, None]
         # a row with no key: SDPA would give NaN; attend anywhere and select 0 (no gradient either)
         live = mask.any(-1, keepdim=True)
-        o = F.scaled_dot_product_attention(qt, kt, vt, attn_mask=mask | ~live, scale=sc)
+        o = F.scaled_dot_product_attention(qt, kt, vt, attn_mask=mask | ~live, dropout_p=dp, scale=sc)
         return torch.where(live, o, torch.zeros_like(o)).transpose(1, 2)
     mask = None
     if kv_len is not None:
@@ -1438,7 +1535,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = 
         if causal:
             mask = mask & torch.ones(q.shape[1], k.shape[1], dtype=torch.bool, device=q.device).tril()
             causal = False
-    o = F.scaled_dot_product_attention(qt, kt, vt, attn_mask=mask, is_causal=causal, scale=sc)
+    o = F.scaled_dot_product_attention(qt, kt, vt, attn_mask=mask, is_causal=causal, dropout_p=dp, scale=sc)
     return o.transpose(1, 2)
 
 

@@ -193,6 +193,49 @@ def uniform01(seed: int, idx: np.ndarray) -> np.ndarray:
     return (h >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
 
 
+# ---- dropout mask identical to common.h dropout_keep ---------------------------------------
+DROP_STREAM_ATTN = 1  # attention probabilities (other dropout sites take other stream ids)
+
+
+def dropout_params(p: float):
+    """(threshold, p_eff) of drop probability ``p``: the mask compares 8-bit hash fields with
+    threshold = round(256 p) (at most 255), so the probability in effect is p_eff = threshold /
+    256 -- kernels, oracle and tests scale by 1 / (1 - p_eff).  Threshold 0: no dropout."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:  # (NaN fails both comparisons)
+        raise ValueError(f"dropout probability must be in [0, 1), got {p}")
+    thr = min(255, int(math.floor(p * 256.0 + 0.5)))
+    return thr, thr / 256.0
+
+
+def dropout_keep(seed: int, p: float, b, h, i, j, stream: int = DROP_STREAM_ATTN) -> np.ndarray:
+    """keep(seed, b, h, i, j) -> bool, broadcast over integer arrays: element (i, j) of head ``h``
+    of batch row ``b`` survives dropout at probability ``p``.  A pure function of its arguments.
+    One hash covers a block of 2 rows x 4 columns as eight 8-bit fields:
+
+        head = splitmix64(splitmix64(seed) ^ (stream << 56 | b << 24 | h))
+        word = splitmix64(head ^ ((i >> 1) << 32 | (j >> 2)))
+        keep = ((word >> (32 (i & 1) + 8 (j & 3))) & 255) >= threshold
+
+    (b < 2^32, h < 2^24, stream < 2^8, i, j < 2^25: disjoint bits, so no two elements share a
+    field.)  common.h dropout_keep is the device twin, bit for bit."""
+    thr, _ = dropout_params(p)
+    b, h, i, j = (np.asarray(t).astype(np.uint64) for t in (b, h, i, j))
+    u = np.uint64
+    with np.errstate(over="ignore"):
+        s0 = _splitmix64(np.array(int(seed) & _M64, dtype=np.uint64))
+        head = _splitmix64(s0 ^ ((u(stream) << u(56)) | (b << u(24)) | h))
+        word = _splitmix64(head ^ (((i >> u(1)) << u(32)) | (j >> u(2))))
+        field = (word >> (u(32) * (i & u(1)) + u(8) * (j & u(3)))) & u(255)
+    return field >= u(thr)
+
+
+def dropout_keep_mask(seed: int, p: float, B: int, H: int, Sq: int, Sk: int) -> torch.Tensor:
+    """bool [B, H, Sq, Sk] of :func:`dropout_keep` over a whole attention problem."""
+    b, h, i, j = np.ogrid[:B, :H, :Sq, :Sk]
+    return torch.from_numpy(np.array(np.broadcast_to(dropout_keep(seed, p, b, h, i, j), (B, H, Sq, Sk))))
+
+
 def q8_encode(x, resid, q, scales, stochastic=False, seed=0):
     v = _f32(x).clone()
     if resid is not None:
@@ -367,7 +410,8 @@ def _bf16_round(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.bfloat16).to(torch.float64)
 
 
-def attention(q, k, v, dout, causal=False, kv_len=None, scale=None, emulate_bf16=False, doc_ids=None, window=None):
+def attention(q, k, v, dout, causal=False, kv_len=None, scale=None, emulate_bf16=False, doc_ids=None, window=None,
+              dropout_p=0.0, dropout_seed=None):
     """fp64 oracle of csrc/attn.hip, forward and an explicit (no autograd) backward.
 
     q / dout [B, Sq, Hq, D], k / v [B, Sk, Hkv, D] (GQA by repetition: query head h reads kv head
@@ -377,16 +421,32 @@ def attention(q, k, v, dout, causal=False, kv_len=None, scale=None, emulate_bf16
     |query - key| >= window.  Returns fp64 (o [B, Sq, Hq, D], lse [B, Hq, Sq], dq, dk, dv).
     A row with every key masked has o = 0, lse = +inf and contributes no gradient.
 
+    ``dropout_p`` > 0 (with an integer ``dropout_seed``): dropout of the attention probabilities by
+    the mask of :func:`dropout_keep`, P_drop = keep * P / (1 - p_eff) with p_eff of
+    :func:`dropout_params`; o = P_drop v, lse is that of P, and with dP = dO v^T
+    dS = P (keep * dP / (1 - p_eff) - delta), delta = rowsum(dO * o), dV = P_drop^T dO.  A p whose
+    threshold is 0 (and the default) is the function without dropout.
+
     ``emulate_bf16`` rounds to bf16 where the kernels do and nowhere else: exp(s - rowmax) before
     P V (the row sum stays unrounded); exp(s - lse) before P^T dO; dS = P (dP - delta) before the
-    dQ and dK products; delta from the rounded o; o / dq / dk / dv themselves (lse to fp32).  Its
-    distance from the unrounded mode is the error a correct bf16 implementation of this algorithm
-    has on the given inputs."""
+    dQ and dK products; delta from the rounded o; o / dq / dk / dv themselves (lse to fp32).  With
+    dropout the same list holds, on keep * exp(s - rowmax) and keep * exp(s - lse): the kernels zero
+    the dropped elements before they round, and apply 1 / (1 - p_eff) in fp32 -- to the P V and the
+    P^T dO accumulators after the products, to dP before delta is subtracted -- so the scale adds no
+    rounding; a one-key row's dS is then not forced to 0 (delta comes from the rounded o = v /
+    (1 - p_eff), as in the kernels).  Its distance from the unrounded mode is the error a correct bf16 implementation of
+    this algorithm has on the given inputs."""
     B, Sq, Hq, D = q.shape
     Sk, Hkv = k.shape[1], k.shape[2]
     G = Hq // Hkv
     sc = float(scale) if scale is not None else 1.0 / math.sqrt(D)
     rnd = _bf16_round if emulate_bf16 else (lambda t: t)
+    keep, rinv = None, 1.0
+    if dropout_params(dropout_p)[0] > 0:
+        if dropout_seed is None:
+            raise ValueError("attention: dropout_p > 0 needs a dropout_seed")
+        keep = dropout_keep_mask(int(dropout_seed), dropout_p, B, Hq, Sq, Sk).to(q.device)
+        rinv = 1.0 / (1.0 - dropout_params(dropout_p)[1])
     qd, dod = (t.to(torch.float64).transpose(1, 2) for t in (q, dout))                    # [B, Hq, Sq, D]
     kd, vd = (t.to(torch.float64).transpose(1, 2).repeat_interleave(G, 1) for t in (k, v))  # [B, Hq, Sk, D]
     keys = torch.arange(Sk, device=q.device)
@@ -412,7 +472,11 @@ def attention(q, k, v, dout, causal=False, kv_len=None, scale=None, emulate_bf16
     m = torch.where(live, s.masked_fill(~mask, -math.inf).amax(-1, keepdim=True), torch.zeros_like(s[..., :1]))
     e = torch.where(mask, torch.exp(s - m), torch.zeros_like(s))
     l = e.sum(-1, keepdim=True)
-    o = torch.where(live, (rnd(e) @ vd) / l.clamp_min(1e-300), torch.zeros_like(qd))
+    if keep is None:
+        o = torch.where(live, (rnd(e) @ vd) / l.clamp_min(1e-300), torch.zeros_like(qd))
+    else:
+        ed = torch.where(keep, e, torch.zeros_like(e))
+        o = torch.where(live, (rnd(ed) @ vd) * rinv / l.clamp_min(1e-300), torch.zeros_like(qd))
     lse = torch.where(live, m + torch.log(l.clamp_min(1e-300)), torch.full_like(m, math.inf))
     o = rnd(o)
     if emulate_bf16:
@@ -420,13 +484,24 @@ def attention(q, k, v, dout, causal=False, kv_len=None, scale=None, emulate_bf16
     # backward: the kernels recompute P from the stored lse
     p = torch.where(mask, torch.exp(s - lse), torch.zeros_like(s))
     delta = (dod * o).sum(-1, keepdim=True)
-    ds = p * (dod @ vd.transpose(-1, -2) - delta)
+    if keep is None:
+        ds = p * (dod @ vd.transpose(-1, -2) - delta)
+    else:
+        dpd = torch.where(keep, (dod @ vd.transpose(-1, -2)) * rinv, torch.zeros_like(p))
+        ds = p * (dpd - delta)
     # a one-key softmax is constant: dS is exactly zero there, not the rounding residue of dP - delta
-    ds = torch.where(mask.sum(-1, keepdim=True) == 1, torch.zeros_like(ds), ds)
+    # (with dropout, kept or dropped: delta = dO . o carries the same factor as dP.  The emulation
+    # keeps what it computed there: the key dropped gives exactly 0, the key kept the residue of
+    # rounding o = v / (1 - p_eff) to bf16, which the kernels' delta has too)
+    if keep is None or not emulate_bf16:
+        ds = torch.where(mask.sum(-1, keepdim=True) == 1, torch.zeros_like(ds), ds)
     ds = rnd(ds)
     dq = (ds @ kd) * sc
     dk = (ds.transpose(-1, -2) @ qd) * sc
-    dv = rnd(p).transpose(-1, -2) @ dod
+    if keep is None:
+        dv = rnd(p).transpose(-1, -2) @ dod
+    else:
+        dv = (rnd(torch.where(keep, p, torch.zeros_like(p))).transpose(-1, -2) @ dod) * rinv
     dk, dv = (t.view(B, Hkv, G, Sk, D).sum(2) for t in (dk, dv))
     return (o.transpose(1, 2), lse.squeeze(-1), rnd(dq).transpose(1, 2), rnd(dk).transpose(1, 2),
             rnd(dv).transpose(1, 2))

@@ -11,6 +11,11 @@ likewise -- so the time ratio can be held against the tile ratio.  ``--docs 1`` 
 every tile of the unbounded kernels, plus the loads of the bounds.
 
     python tools/diag/attn_time.py --docs 8 [--window 512] [--json out.json]
+
+With ``--dropout P`` it times the DROP kernels (attention dropout at probability P, the mask
+generated in the kernels) against the plain ones, per shape: plain, dropout, plain again.
+
+    python tools/diag/attn_time.py --dropout 0.1 --iters 200 [--json out.json]
 """
 import argparse
 import json
@@ -105,6 +110,37 @@ def _masked(a):
     return out
 
 
+def _dropout(a):
+    """--dropout P: the DROP kernels (in-kernel mask at probability P) against the plain ones, each
+    shape's four figures from one process, interleaved."""
+    out = {}
+    for name, (B, S, Hq, Hkv, D, causal) in SHAPES.items():
+        if a.only and a.only not in name:
+            continue
+        torch.manual_seed(0)
+        q = torch.randn(B, S, Hq, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+        k = torch.randn(B, S, Hkv, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+        v = torch.randn(B, S, Hkv, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+        g = torch.randn(B, S, Hq, D, device="cuda", dtype=torch.bfloat16)
+        row = {}
+        for tag, p in (("plain", 0.0), ("dropout", a.dropout), ("plain_again", 0.0)):
+            f = lambda p=p: hnn.attention(q, k, v, causal=causal, dropout_p=p, dropout_seed=1234)  # noqa: E731
+            with torch.no_grad():
+                tf = _time(f)
+            o = f()
+            tb = _time(lambda: torch.autograd.grad(o, (q, k, v), g, retain_graph=True))
+            row[tag] = {"fwd_ms": round(tf, 4), "bwd_ms": round(tb, 4)}
+        d, u = row["dropout"], row["plain"]
+        row["ratio"] = {x: round(d[x] / u[x], 4) for x in ("fwd_ms", "bwd_ms")}
+        out[name] = row
+        print(f"{name:16s} fwd {u['fwd_ms']:.3f} -> {d['fwd_ms']:.3f} ms (x{row['ratio']['fwd_ms']:.3f}) | bwd "
+              f"{u['bwd_ms']:.3f} -> {d['bwd_ms']:.3f} ms (x{row['ratio']['bwd_ms']:.3f}) | plain again fwd "
+              f"{row['plain_again']['fwd_ms']:.3f} bwd {row['plain_again']['bwd_ms']:.3f}", flush=True)
+        del q, k, v, g
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     global ITERS
     ap = argparse.ArgumentParser()
@@ -113,8 +149,16 @@ def main():
     ap.add_argument("--docs", type=int, default=0, help="N equal documents per row (row-range kernels)")
     ap.add_argument("--window", type=int, default=0, help="sliding window of W keys (row-range kernels)")
     ap.add_argument("--iters", type=int, default=ITERS, help="timed calls per figure (the median is kept)")
+    ap.add_argument("--dropout", type=float, default=0.0, help="attention dropout P: DROP kernels vs the plain ones")
     a = ap.parse_args()
     ITERS = a.iters
+    if a.dropout:
+        out = _dropout(a)
+        if a.json:
+            os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
+            with open(a.json, "w") as f:
+                json.dump({"dropout_p": a.dropout, "iters": ITERS, "shapes": out}, f, indent=1)
+        return
     if a.docs or a.window:
         out = _masked(a)
         if a.json:

@@ -59,6 +59,13 @@ void bn_backward_partials(at::Tensor part, int64_t nrb, at::Tensor dy, at::Tenso
                           at::Tensor weight, at::Tensor mean, at::Tensor invstd, at::Tensor scale, at::Tensor shift,
                           at::Tensor dx, c10::optional<at::Tensor> dres, at::Tensor dweight, at::Tensor dbias, int64_t C,
                           c10::optional<at::Tensor> mask_in, int64_t unr);
+void bn_apply_bits(at::Tensor x, at::Tensor res, at::Tensor y, at::Tensor mask, at::Tensor scale, at::Tensor shift,
+                   c10::optional<at::Tensor> rscale, c10::optional<at::Tensor> rshift, int64_t C);
+// bnconv.hip
+int64_t bnconv_mtiles(int64_t M);
+void bnconv_forward(at::Tensor x3, at::Tensor res, at::Tensor scale, at::Tensor shift,
+                    c10::optional<at::Tensor> rscale, c10::optional<at::Tensor> rshift, at::Tensor w, at::Tensor out,
+                    at::Tensor bits, at::Tensor y, at::Tensor part);
 // gemm.hip
 int64_t conv1x1_mtiles(int64_t M);
 void conv1x1_forward(at::Tensor x, at::Tensor w, at::Tensor y, c10::optional<at::Tensor> part, int64_t Hi,
@@ -224,6 +231,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("part"), py::arg("nrb"), py::arg("dy"), py::arg("x"), py::arg("mask_mode"), py::arg("weight"),
         py::arg("mean"), py::arg("invstd"), py::arg("scale"), py::arg("shift"), py::arg("dx"), py::arg("dres"),
         py::arg("dweight"), py::arg("dbias"), py::arg("C"), py::arg("mask_in"), py::arg("unr") = 0);
+  m.def("bn_apply_bits", &hipps::bn_apply_bits,
+        "y = relu(x*scale + shift + res [*rscale + rshift]) and its ReLU bits (the apply pass alone)", py::arg("x"),
+        py::arg("res"), py::arg("y"), py::arg("mask"), py::arg("scale"), py::arg("shift"),
+        py::arg("rscale") = py::none(), py::arg("rshift") = py::none(), py::arg("C"));
+  m.def("bnconv_mtiles", &hipps::bnconv_mtiles);
+  m.def("bnconv_forward", &hipps::bnconv_forward,
+        "out = relu(bn(x3) + residual) with its ReLU bits, y = out . w^T and y's BN statistics partials, one kernel",
+        py::arg("x3"), py::arg("res"), py::arg("scale"), py::arg("shift"), py::arg("rscale") = py::none(),
+        py::arg("rshift") = py::none(), py::arg("w"), py::arg("out"), py::arg("bits"), py::arg("y"), py::arg("part"));
   m.def("conv1x1_mtiles", &hipps::conv1x1_mtiles);
   m.def("bn_dual_forward", &hipps::bn_dual_forward,
         "z = relu(bn3(x3) + bnd(xd)) from producer partials: two finalizes + one apply (downsample block)");

@@ -762,6 +762,33 @@ void bn_apply(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor y, at::Ten
                      shift.data_ptr<float>(), M, (int)C, (int)relu, nullptr, nullptr, bits_pack());
 }
 
+// The apply pass of a training BN + residual + ReLU alone, from an already finalized scale / shift:
+// y = relu(x*scale + shift + r), r = res or res*rscale + rshift, and the ReLU bits of y.  This is
+// the pass bn_forward_partials / bn_dual_forward launch after their finalize; a block output whose
+// apply was left to the next block's conv1 (bnconv.hip) and found no such consumer runs it.
+void bn_apply_bits(at::Tensor x, at::Tensor res, at::Tensor y, at::Tensor mask, at::Tensor scale, at::Tensor shift,
+                   c10::optional<at::Tensor> rscale, c10::optional<at::Tensor> rshift, int64_t C) {
+  TORCH_CHECK(C % 8 == 0 && C <= kMaxC && C >= 8, "fused BN needs C % 8 == 0 and 8 <= C <= 2048");
+  const int64_t M = x.numel() / C;
+  check_act(x, "x", M * C);
+  check_act(res, "residual", M * C);
+  check_act(y, "y", M * C);
+  TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == at::kByte && mask.numel() == M * C / 8, "mask: uint8[M*C/8]");
+  check_vec(scale, "scale", (int)C);
+  check_vec(shift, "shift", (int)C);
+  const bool dual = rscale.has_value() && rscale->defined();
+  TORCH_CHECK(dual == (rshift.has_value() && rshift->defined()), "rscale and rshift come together");
+  if (dual) {
+    check_vec(*rscale, "rscale", (int)C);
+    check_vec(*rshift, "rshift", (int)C);
+  }
+  hipLaunchKernelGGL(apply_fwd_kernel(M, (int)C), apply_grid(M, (int)C), kBlock, 0, c10::hip::getCurrentHIPStream(),
+                     (const uint16_t*)x.data_ptr(), (const uint16_t*)res.data_ptr(), (uint16_t*)y.data_ptr(),
+                     (uint8_t*)mask.data_ptr(), scale.data_ptr<float>(), shift.data_ptr<float>(), M, (int)C, 1,
+                     dual ? rscale->data_ptr<float>() : nullptr, dual ? rshift->data_ptr<float>() : nullptr,
+                     bits_pack());
+}
+
 // returns nothing; writes dx (and dres), dweight, dbias
 void bn_backward(at::Tensor dy, at::Tensor x, c10::optional<at::Tensor> y, int64_t mask_mode, at::Tensor weight,
                  at::Tensor mean, at::Tensor invstd, at::Tensor scale, at::Tensor shift, at::Tensor dx,

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from hipps.ops.nn import (FusedBatchNorm2d, Linear, MaxPool2d, ResidualTap, bn_pro_pays, bn_relu_conv, bn_relu_conv1x1_ok,
                           bn_relu_conv_bn, bn_relu_conv_ok, bn_relu_maxpool, conv1x1_bn_input, conv1x1_ok, conv2d,
-                          conv2d_bn, conv2d_stats, conv_bn, dual_bn_relu, dual_bn_relu_ok, global_avg_pool,
+                          conv2d_bn, conv2d_stats, conv_bn, dual_bn_relu, dual_bn_relu_ok, global_avg_pool, materialize,
                           stem_block, stem_block_ok)
 
 # One switch for the whole zoo: fused BN(+residual)(+ReLU) HIP kernels on channels-last bf16,
@@ -134,7 +134,9 @@ class Bottleneck(nn.Module):
             return dual_bn_relu(self.bn3, x3, p3, ds[1], xd, pd)
         return self.bn3(x3, ds[1](xd, stats=pd), stats=p3)
 
-    def forward(self, x):
+    def forward(self, x, defer_out: bool = False):
+        # defer_out: leave bn3's apply pass (+ residual + ReLU) to the reader of the result, the next
+        # block's conv1 (ops.nn.DeferredApply; forward_blocks decides and flushes)
         # Gradient of x = conv1's dgrad + the residual path's gradient.  Instead of autograd's add
         # (read 2, write 1 full-size tensors per block) conv1's dgrad epilogue sums them: the
         # identity residual's gradient (bn3's dy * ReLU bits) arrives through a ResidualTap, a
@@ -167,7 +169,7 @@ class Bottleneck(nn.Module):
                 y = self.bn2(x2, stats=p2) if p2 is not None and self.bn2._fast_ok(x2, None) else self.bn2(x2)
                 x3, p3 = conv1x1_bn_input(self.conv3, y, bn_grad=bng)
             if dual_bn_relu_ok(self.bn3, ds[1], x3, xd):
-                return dual_bn_relu(self.bn3, x3, p3, ds[1], xd, pd)
+                return dual_bn_relu(self.bn3, x3, p3, ds[1], xd, pd, defer=defer_out)
             return self.bn3(x3, ds[1](xd, stats=pd), stats=p3)
         else:
             if _FUSED_GRAD:
@@ -189,12 +191,30 @@ class Bottleneck(nn.Module):
                     bn_pro_pays(self.bn2, self.conv3, x2, p2)):
                 # bn2 + ReLU in conv3's operand prologue (this layer measured faster that way)
                 x3, p3 = bn_relu_conv(self.bn2, self.conv3, x2, p2)
-                return self.bn3(x3, idt, stats=p3, res_tap=tap) if self.bn3._fast_ok(x3, idt) else self.bn3(x3, idt)
+                if self.bn3._fast_ok(x3, idt):
+                    return self.bn3(x3, idt, stats=p3, res_tap=tap, defer=defer_out)
+                return self.bn3(x3, idt)
             if p2 is not None and self.bn2.training and self.bn2._fast_ok(x2, None):
                 y = self.bn2(x2, stats=p2)
             else:
                 y = self.bn2(x2)
-        return conv_bn(self.conv3, self.bn3, y, residual=idt, fuse=_FUSED_CONV, res_tap=tap, bn_grad=bng)
+        return conv_bn(self.conv3, self.bn3, y, residual=idt, fuse=_FUSED_CONV, res_tap=tap, bn_grad=bng,
+                       defer=defer_out)
+
+
+def forward_blocks(blocks, x):
+    """Run ``blocks`` in sequence.  In training, a Bottleneck followed by another Bottleneck leaves its
+    output's apply pass to that block's conv1 (one kernel instead of two where the tuner measured it
+    faster, HIPPS_FUSED_BNCONV); whatever comes out at the end is materialised."""
+    blocks = list(blocks)
+    for i, b in enumerate(blocks):
+        nxt = blocks[i + 1] if i + 1 < len(blocks) else None
+        if (_FUSED_GRAD and isinstance(b, Bottleneck) and isinstance(nxt, Bottleneck) and b.training and
+                nxt.training and torch.is_grad_enabled()):
+            x = b(x, defer_out=True)
+        else:
+            x = b(x)
+    return materialize(x)
 
 
 class BasicBlock(nn.Module):
@@ -256,8 +276,7 @@ class ResNet(nn.Module):
         else:
             y, part = conv2d_stats(self.conv1, x, fuse=_FUSED_STEM)
             x = bn_relu_maxpool(self.bn1, self.maxpool, y, part if _FUSED_STEM_POOL else None)
-        for i in range(self.num_stages):
-            x = getattr(self, f"layer{i + 1}")(x)
+        x = forward_blocks([b for i in range(self.num_stages) for b in getattr(self, f"layer{i + 1}")], x)
         x = global_avg_pool(x)
         return self.fc(x)
 

@@ -94,6 +94,9 @@ _BN_PRO_TUNE = _os.environ.get("HIPPS_BN_PRO_TUNE", "1") != "0"
 _STEM_BWD_DY = _os.environ.get("HIPPS_FUSED_STEMBWD", "2") == "2"
 # ... its pool-gradient recompute over 2x2 pixel blocks (one window gather per four pixels); 0: per pixel
 _STEM_QUAD = _os.environ.get("HIPPS_STEM_QUAD", "1") != "0"
+# ResNet block boundary: bn3's apply pass (+ residual + ReLU) of block i inside conv1 of block i+1
+# (csrc/bnconv.hip, DeferredApply), per layer where measured faster than the two kernels; 0: never
+_FUSED_BNCONV = _os.environ.get("HIPPS_FUSED_BNCONV", "1") != "0"
 _WG_STREAMS: dict = {}
 _WG_JOINED: dict = {}  # device -> autograd graph task whose end joins the side stream
 
@@ -632,6 +635,76 @@ class S2Tap:
 
     def __init__(self):
         self.dx = None
+
+
+class DeferredApply:
+    """The apply pass of a block's last BN -- out = relu(x3 * scale + shift + r), r = res or (a
+    downsample block) res * rscale + rshift, and out's ReLU bits -- left to the consumer of out.
+    The BN's finalize has run (scale / shift, running statistics), ``out`` and ``bits`` are
+    allocated and everything the backward uses refers to them, but nothing has written them yet:
+    the next block's conv1 does, in the GEMM that consumes out (csrc/bnconv.hip), instead of
+    reading back what a separate apply kernel wrote.  The record rides on ``out`` as
+    ``_hipps_pending``; a reader that is not such a conv1 calls ``materialize(out)`` first, which
+    runs the plain apply kernel."""
+
+    __slots__ = ("x3", "res", "scale", "shift", "rscale", "rshift", "out", "bits", "done")
+
+    def __init__(self, x3, res, scale, shift, rscale, rshift, out, bits):
+        self.x3, self.res, self.scale, self.shift, self.rscale, self.rshift = x3, res, scale, shift, rscale, rshift
+        self.out, self.bits = out, bits
+        self.done = False
+
+    def apply(self):
+        native().bn_apply_bits(self.x3, self.res, self.out, self.bits, self.scale, self.shift, self.rscale,
+                               self.rshift, self.x3.shape[1])
+
+    def flush(self):
+        if not self.done:
+            self.apply()
+            self.done = True
+
+
+def materialize(x):
+    """x, with a deferred apply pass (DeferredApply) that no conv1 took over run now."""
+    pend = getattr(x, "_hipps_pending", None)
+    if pend is not None:
+        pend.flush()
+        x._hipps_pending = None
+    return x
+
+
+def _bnconv_fwd(pend: DeferredApply, x, w2d, y, Hi, Wi):
+    """conv1 on a block output whose apply pass is still pending: writes pend.out (= x), its ReLU
+    bits and y, returns y's statistics partials.  Two routes, chosen per shape by measurement on
+    the real operands (tuner kind 'bnconv'): "separate" = the apply kernel + the tuned 1x1 GEMM,
+    "fused" = one kernel (bnconv.hip).  The BN's finalize precedes both and is not timed.  The
+    fused kernel's row tile is 128 high, split like gemm2's 128-row tiles: it is offered only
+    where the shape's recorded 1x1 pick has that height, so both routes give the same bits (y's
+    partials included) and the choice cannot change a result."""
+    C = native()
+    N, K = w2d.shape
+    M = y.numel() // N
+
+    def separate():
+        pend.apply()
+        return _conv1x1_gemm(x, w2d, y, Hi, Wi, 1, True)
+
+    def fused():
+        part = torch.empty((2, N, C.bnconv_mtiles(M)), dtype=torch.float32, device=y.device)
+        C.bnconv_forward(pend.x3, pend.res, pend.scale, pend.shift, pend.rscale, pend.rshift, w2d, pend.out, pend.bits,
+                         y, part)
+        return part
+
+    # (the first call for a shape runs the separate route, which measures the plain GEMM's pick)
+    plain = TUNER.cache.get(("1x1", M, K, N, 1, Hi, Wi, (True, False, False, False, False, False)))
+    same_tiles = plain is not None and (_g2_parse(plain)[0] == 128 if plain != "g1" else N % 128 == 0)
+    name = "separate"
+    if same_tiles:
+        name = TUNER.pick(("bnconv", M, K, N, pend.rscale is not None), ["separate", "fused"],
+                          lambda n: fused() if n == "fused" else separate())
+    part = fused() if name == "fused" else separate()
+    pend.done = True
+    return part
 
 
 _SHADOWS: list = []  # [fp32 flat param buffer, bf16 shadow] pairs (FlatStore.enable_bf16_shadow)
@@ -1848,7 +1921,7 @@ class _Conv1x1(torch.autograd.Function):
     and with ``alias`` the gradient of the returned alias of x (e.g. a downsample branch)."""
 
     @staticmethod
-    def forward(ctx, x, w_master, stride, tap=None, alias=False, bngrad=None, s2tap=None):
+    def forward(ctx, x, w_master, stride, tap=None, alias=False, bngrad=None, s2tap=None, pend=None):
         w = bf16_weight(w_master)
         ctx.wdtype = w_master.dtype
         ctx.wparam = w_master
@@ -1860,7 +1933,10 @@ class _Conv1x1(torch.autograd.Function):
         Cout = w.shape[0]
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
         y = torch.empty((N, Cout, Ho, Wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-        part = _conv1x1_gemm(x, w.reshape(Cout, Cin), y, H, W, stride, True)
+        if pend is not None:  # x's own apply pass is still pending: this GEMM produces x too
+            part = _bnconv_fwd(pend, x, w.reshape(Cout, Cin), y, H, W)
+        else:
+            part = _conv1x1_gemm(x, w.reshape(Cout, Cin), y, H, W, stride, True)
         ctx.stride = stride
         ctx.tap = tap
         # alias (conv1): the downsample's compact gradient arrives here; stride 2 (downsample): put
@@ -1881,7 +1957,7 @@ class _Conv1x1(torch.autograd.Function):
             ctx.bngrad = None
             if s2tap is not None and s2tap.dx is not None:
                 raise RuntimeError("compact stride-2 gradient without a consuming dgrad")
-            return d_alias, None, None, None, None, None, None
+            return d_alias, None, None, None, None, None, None, None
         dy = dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         dx = dw = None
         add, add_mask = ctx.tap.take() if ctx.tap is not None else (None, None)
@@ -1940,7 +2016,7 @@ class _Conv1x1(torch.autograd.Function):
             else:
                 _conv1x1_gemm(dy, wt, dx, x.shape[2], x.shape[3], 1, False, add, add_mask, None, add_s2)
         ctx.bngrad = None
-        return dx, dw, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None
 
 
 class _BNReluConv1x1(torch.autograd.Function):
@@ -2245,16 +2321,17 @@ def conv1x1_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
     return conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0
 
 
-def conv1x1_stats(x, weight, stride=1, tap=None, alias=False, bngrad=None, s2tap=None):
+def conv1x1_stats(x, weight, stride=1, tap=None, alias=False, bngrad=None, s2tap=None, pend=None):
     """(y, part[, x_alias]): bf16 1x1 conv output and its [2, Cout, m_tiles] BN partial
     statistics (see _Conv1x1 for ``tap`` / ``alias``, BNGradTap for ``bngrad``, S2Tap for
-    ``s2tap``)."""
-    return _Conv1x1.apply(x, weight, int(stride), tap, bool(alias), bngrad, s2tap)
+    ``s2tap``, DeferredApply for ``pend``)."""
+    return _Conv1x1.apply(x, weight, int(stride), tap, bool(alias), bngrad, s2tap, pend)
 
 
 class _FusedBNAct(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, res, weight, bias, running_mean, running_var, eps, momentum, relu, part=None, tap=None):
+    def forward(ctx, x, res, weight, bias, running_mean, running_var, eps, momentum, relu, part=None, tap=None,
+                defer=False):
         C = x.shape[1]
         y = torch.empty_like(x, memory_format=torch.channels_last)
         f32 = dict(dtype=torch.float32, device=x.device)
@@ -2264,7 +2341,12 @@ class _FusedBNAct(torch.autograd.Function):
         # re-reading the bf16 output in the backward
         mode = MASK_NONE if not relu else (MASK_BITS if res is not None else MASK_X)
         mask = torch.empty(x.numel() // 8, dtype=torch.uint8, device=x.device) if mode == MASK_BITS else None
-        if part is not None:  # statistics already reduced by the producing 1x1 conv
+        if defer and part is not None and mode == MASK_BITS:
+            # finalize only: the consumer of y (the next block's conv1) runs the apply pass (DeferredApply)
+            native().bn_finalize_partials(part, part.shape[2], x.numel() // C, weight, bias, running_mean, running_var,
+                                          mean, invstd, scale, shift, C, float(eps), float(momentum))
+            y._hipps_pending = DeferredApply(x, res, scale, shift, None, None, y, mask)
+        elif part is not None:  # statistics already reduced by the producing 1x1 conv
             native().bn_forward_partials(part, part.shape[2], x, res, y, weight, bias, running_mean, running_var,
                                          mean, invstd, scale, shift, C, float(eps), float(momentum), bool(relu), mask)
         else:
@@ -2300,7 +2382,7 @@ class _FusedBNAct(torch.autograd.Function):
                                  mask)
         if tap is not None:
             tap.dy, tap.mask = dy, (mask if ctx.mode == MASK_BITS else None)
-        return dx, dres, dw, db, None, None, None, None, None, None, None
+        return dx, dres, dw, db, None, None, None, None, None, None, None, None
 
 
 class _DualBNRelu(torch.autograd.Function):
@@ -2313,15 +2395,21 @@ class _DualBNRelu(torch.autograd.Function):
     (BNGradTap on z, as for _FusedBNAct)."""
 
     @staticmethod
-    def forward(ctx, x3, part3, w3, b3, rm3, rv3, eps3, mom3, xd, partd, wd, bd, rmd, rvd, epsd, momd):
+    def forward(ctx, x3, part3, w3, b3, rm3, rv3, eps3, mom3, xd, partd, wd, bd, rmd, rvd, epsd, momd, defer=False):
         C = x3.shape[1]
         f32 = dict(dtype=torch.float32, device=x3.device)
         v3 = [torch.empty(C, **f32) for _ in range(4)]
         vd = [torch.empty(C, **f32) for _ in range(4)]
         z = torch.empty_like(x3, memory_format=torch.channels_last)
         mask = torch.empty(x3.numel() // 8, dtype=torch.uint8, device=x3.device)
-        native().bn_dual_forward(part3, part3.shape[2], partd, partd.shape[2], x3, xd, z, mask, w3, b3, rm3, rv3, *v3,
-                                 wd, bd, rmd, rvd, *vd, C, float(eps3), float(mom3), float(epsd), float(momd))
+        if defer:  # the two finalizes only: z's consumer runs the apply pass (DeferredApply)
+            M = x3.numel() // C
+            native().bn_finalize_partials(part3, part3.shape[2], M, w3, b3, rm3, rv3, *v3, C, float(eps3), float(mom3))
+            native().bn_finalize_partials(partd, partd.shape[2], M, wd, bd, rmd, rvd, *vd, C, float(epsd), float(momd))
+            z._hipps_pending = DeferredApply(x3, xd, v3[2], v3[3], vd[2], vd[3], z, mask)
+        else:
+            native().bn_dual_forward(part3, part3.shape[2], partd, partd.shape[2], x3, xd, z, mask, w3, b3, rm3, rv3,
+                                     *v3, wd, bd, rmd, rvd, *vd, C, float(eps3), float(mom3), float(epsd), float(momd))
         ctx.C = C
         ctx.save_for_backward(x3, xd, mask, w3, v3[0], v3[1], wd, vd[0], vd[1])
         ctx.bngrad = BNGradTap(x3, mask, v3[0], v3[1], v3[2], v3[3])
@@ -2341,7 +2429,7 @@ class _DualBNRelu(torch.autograd.Function):
         dw3, db3, dwd, dbd = (torch.empty_like(w3) for _ in range(4))
         native().bn_dual_backward(part3, 0 if part3 is None else part3.shape[2], dz, x3, xd, mask, w3, mean3, invstd3,
                                   wd, meand, invstdd, dx3, dxd, dw3, db3, dwd, dbd, ctx.C)
-        return dx3, None, dw3, db3, None, None, None, None, dxd, None, dwd, dbd, None, None, None, None
+        return dx3, None, dw3, db3, None, None, None, None, dxd, None, dwd, dbd, None, None, None, None, None
 
 
 def dual_bn_relu_ok(bn3, bnd, x3, xd) -> bool:
@@ -2351,14 +2439,16 @@ def dual_bn_relu_ok(bn3, bnd, x3, xd) -> bool:
             bnd.weight.dtype == torch.float32)
 
 
-def dual_bn_relu(bn3, x3, part3, bnd, xd, partd):
+def dual_bn_relu(bn3, x3, part3, bnd, xd, partd, defer: bool = False):
     """relu(bn3(x3) + bnd(xd)) with both BNs' statistics partials from their producers
-    (callers check dual_bn_relu_ok first)."""
+    (callers check dual_bn_relu_ok first).  ``defer``: leave the apply pass to the consumer
+    (DeferredApply; the caller guarantees that a conv_bn / conv1x1_bn_input or materialize reads it
+    first)."""
     bn3._nbt_pending += 1
     bnd._nbt_pending += 1
     return _DualBNRelu.apply(x3, part3, bn3.weight, bn3.bias, bn3.running_mean, bn3.running_var, bn3.eps,
                              bn3.momentum, xd, partd, bnd.weight, bnd.bias, bnd.running_mean, bnd.running_var,
-                             bnd.eps, bnd.momentum)
+                             bnd.eps, bnd.momentum, bool(defer) and _FUSED_BNCONV)
 
 
 def conv1x1_bn_input(conv: nn.Conv2d, x, tap=None, alias: bool = False, bn_grad: bool = False):
@@ -2369,7 +2459,7 @@ def conv1x1_bn_input(conv: nn.Conv2d, x, tap=None, alias: bool = False, bn_grad:
     own_tap = tap if s == 1 else None
     bg = getattr(x, "_hipps_bngrad", None) if bn_grad else None
     s2tap = S2Tap() if (alias and s == 1) else (getattr(x, "_hipps_s2tap", None) if s == 2 else None)
-    outs = conv1x1_stats(x, conv.weight, s, own_tap, alias and s == 1, bg, s2tap)
+    outs = conv1x1_stats(x, conv.weight, s, own_tap, alias and s == 1, bg, s2tap, _take_pending(x, s))
     if own_tap is not None:
         own_tap.armed = True
     if alias and s == 1:
@@ -2377,14 +2467,29 @@ def conv1x1_bn_input(conv: nn.Conv2d, x, tap=None, alias: bool = False, bn_grad:
     return outs
 
 
+def _take_pending(x, stride):
+    """x's pending apply pass for the stride-1 1x1 GEMM about to read x (it then writes x too); a
+    strided conv gets x materialised and None."""
+    pend = getattr(x, "_hipps_pending", None)
+    if pend is None:
+        return None
+    if stride != 1 or pend.done:
+        materialize(x)
+        return None
+    x._hipps_pending = None
+    return pend
+
+
 def fused_bn_act(x, weight, bias, running_mean, running_var, eps=1e-5, momentum=0.1, relu=True, residual=None,
-                 part=None, res_tap=None):
+                 part=None, res_tap=None, defer=False):
     """Training-mode BN (+residual) (+ReLU) on a channels-last bf16 HIP tensor.  ``part``: the
     [2, C, nrb] partial statistics when the producer (conv1x1_stats) already reduced them.
     ``res_tap``: an armed ResidualTap -- the residual's gradient goes to its consumer instead
-    of autograd (the residual input then receives no gradient from this op)."""
+    of autograd (the residual input then receives no gradient from this op).  ``defer`` (with
+    ``part``, a residual and ReLU): finalize only, the apply pass is left to the consumer
+    (DeferredApply)."""
     return _FusedBNAct.apply(x, residual, weight, bias, running_mean, running_var, eps, momentum, relu, part,
-                             res_tap)
+                             res_tap, bool(defer) and _FUSED_BNCONV)
 
 
 class FusedBatchNorm2d(nn.BatchNorm2d):
@@ -2423,13 +2528,13 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
             return False
         return True
 
-    def forward(self, x, residual=None, stats=None, res_tap=None):
+    def forward(self, x, residual=None, stats=None, res_tap=None, defer=False):
         if self._fast_ok(x, residual):
             if self.training:
                 self._nbt_pending += 1
                 tap = res_tap if (res_tap is not None and res_tap.armed and residual is not None) else None
                 return fused_bn_act(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
-                                    self.momentum, self.relu, residual, stats, tap)
+                                    self.momentum, self.relu, residual, stats, tap, defer)
             if not torch.is_grad_enabled() or not (x.requires_grad or (residual is not None and
                                                                        residual.requires_grad)):
                 scale = self.weight / torch.sqrt(self.running_var + self.eps)
@@ -2447,7 +2552,7 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
 
 
 def conv_bn(conv: nn.Conv2d, bn: FusedBatchNorm2d, x, residual=None, fuse: bool = True, tap=None, res_tap=None,
-            alias: bool = False, bn_grad: bool = False):
+            alias: bool = False, bn_grad: bool = False, defer: bool = False):
     """bn(conv(x), residual): a 1x1 conv that feeds a training-mode fused BN runs as the MFMA GEMM
     with the BN statistics in its epilogue (one fewer pass over the conv output).
 
@@ -2459,7 +2564,10 @@ def conv_bn(conv: nn.Conv2d, bn: FusedBatchNorm2d, x, residual=None, fuse: bool 
                -> returns (out, x_alias)
       bn_grad  x is the output of a fused BN whose only gradient is this conv's input gradient
                (after the tap / alias sums): reduce that BN's backward statistics in the dgrad
-               epilogue (BNGradTap)"""
+               epilogue (BNGradTap)
+      defer    leave bn's apply pass to the consumer of the result (DeferredApply): the caller
+               guarantees that the next reader is a conv_bn / conv1x1_bn_input or materialize
+    An x whose own apply pass is pending is written by this conv's GEMM (or materialised first)."""
     if fuse and bn.training and conv1x1_ok(conv, x):
         s = conv.stride[0]
         own_tap = tap if s == 1 else None
@@ -2467,16 +2575,19 @@ def conv_bn(conv: nn.Conv2d, bn: FusedBatchNorm2d, x, residual=None, fuse: bool 
         # alias (conv1 of a downsample block): its dgrad takes the downsample's compact gradient;
         # stride 2 reading such an alias (the downsample): hand that gradient over (S2Tap)
         s2tap = S2Tap() if (alias and s == 1) else (getattr(x, "_hipps_s2tap", None) if s == 2 else None)
-        outs = conv1x1_stats(x, conv.weight, s, own_tap, alias and s == 1, bg, s2tap)
+        outs = conv1x1_stats(x, conv.weight, s, own_tap, alias and s == 1, bg, s2tap, _take_pending(x, s))
         y, part = outs[0], outs[1]
         xa = outs[2] if len(outs) > 2 else x
         if alias and s == 1 and s2tap is not None:
             xa._hipps_s2tap = s2tap
         if own_tap is not None:
             own_tap.armed = True
-        out = bn(y, residual, stats=part, res_tap=res_tap) if bn._fast_ok(y, residual) else bn(y, residual)
+        if bn._fast_ok(y, residual):
+            out = bn(y, residual, stats=part, res_tap=res_tap, defer=defer)
+        else:
+            out = bn(y, residual)
     else:
-        xa = x
+        xa = materialize(x)
         out = bn(conv(x), residual)
     return (out, xa) if alias else out
 

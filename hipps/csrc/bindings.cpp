@@ -59,6 +59,8 @@ void bn_backward_partials(at::Tensor part, int64_t nrb, at::Tensor dy, at::Tenso
                           at::Tensor weight, at::Tensor mean, at::Tensor invstd, at::Tensor scale, at::Tensor shift,
                           at::Tensor dx, c10::optional<at::Tensor> dres, at::Tensor dweight, at::Tensor dbias, int64_t C,
                           c10::optional<at::Tensor> mask_in, int64_t unr);
+void bn_backward_apply(at::Tensor dy, at::Tensor x, int64_t mask_mode, at::Tensor scale, at::Tensor shift,
+                       at::Tensor coef, at::Tensor dx, int64_t C, c10::optional<at::Tensor> mask_in, int64_t unr);
 void bn_apply_bits(at::Tensor x, at::Tensor res, at::Tensor y, at::Tensor mask, at::Tensor scale, at::Tensor shift,
                    c10::optional<at::Tensor> rscale, c10::optional<at::Tensor> rshift, int64_t C);
 // bnconv.hip
@@ -66,6 +68,9 @@ int64_t bnconv_mtiles(int64_t M);
 void bnconv_forward(at::Tensor x3, at::Tensor res, at::Tensor scale, at::Tensor shift,
                     c10::optional<at::Tensor> rscale, c10::optional<at::Tensor> rshift, at::Tensor w, at::Tensor out,
                     at::Tensor bits, at::Tensor y, at::Tensor part);
+void bnconv_backward(at::Tensor dy, at::Tensor x3, at::Tensor bits, at::Tensor coef, at::Tensor wt, at::Tensor dx3,
+                     at::Tensor dbn, at::Tensor part, at::Tensor bn_x, at::Tensor bn_mean, at::Tensor bn_invstd,
+                     at::Tensor bn_scale, at::Tensor bn_shift, int64_t bn);
 // gemm.hip
 int64_t conv1x1_mtiles(int64_t M);
 void conv1x1_forward(at::Tensor x, at::Tensor w, at::Tensor y, c10::optional<at::Tensor> part, int64_t Hi,
@@ -231,6 +236,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("part"), py::arg("nrb"), py::arg("dy"), py::arg("x"), py::arg("mask_mode"), py::arg("weight"),
         py::arg("mean"), py::arg("invstd"), py::arg("scale"), py::arg("shift"), py::arg("dx"), py::arg("dres"),
         py::arg("dweight"), py::arg("dbias"), py::arg("C"), py::arg("mask_in"), py::arg("unr") = 0);
+  m.def("bn_backward_apply", &hipps::bn_backward_apply,
+        "BN bwd apply pass alone, dx = a*dz + k1*x + k0 with coef [3, C] from bn_finalize_bwd_partials", py::arg("dy"),
+        py::arg("x"), py::arg("mask_mode"), py::arg("scale"), py::arg("shift"), py::arg("coef"), py::arg("dx"),
+        py::arg("C"), py::arg("mask_in"), py::arg("unr") = 0);
   m.def("bn_apply_bits", &hipps::bn_apply_bits,
         "y = relu(x*scale + shift + res [*rscale + rshift]) and its ReLU bits (the apply pass alone)", py::arg("x"),
         py::arg("res"), py::arg("y"), py::arg("mask"), py::arg("scale"), py::arg("shift"),
@@ -240,6 +249,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out = relu(bn(x3) + residual) with its ReLU bits, y = out . w^T and y's BN statistics partials, one kernel",
         py::arg("x3"), py::arg("res"), py::arg("scale"), py::arg("shift"), py::arg("rscale") = py::none(),
         py::arg("rshift") = py::none(), py::arg("w"), py::arg("out"), py::arg("bits"), py::arg("y"), py::arg("part"));
+  m.def("bnconv_backward", &hipps::bnconv_backward,
+        "dx3 = bn3's input gradient (a*dz + k1*x3 + k0), dbn = dx3 . wt^T and the backward reduction partials of the "
+        "BN whose output gradient dbn is, one kernel",
+        py::arg("dy"), py::arg("x3"), py::arg("bits"), py::arg("coef"), py::arg("wt"), py::arg("dx3"), py::arg("dbn"),
+        py::arg("part"), py::arg("bn_x"), py::arg("bn_mean"), py::arg("bn_invstd"), py::arg("bn_scale"),
+        py::arg("bn_shift"), py::arg("bn") = 0);
   m.def("conv1x1_mtiles", &hipps::conv1x1_mtiles);
   m.def("bn_dual_forward", &hipps::bn_dual_forward,
         "z = relu(bn3(x3) + bnd(xd)) from producer partials: two finalizes + one apply (downsample block)");

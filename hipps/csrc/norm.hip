@@ -904,6 +904,41 @@ void bn_forward_partials(at::Tensor part, int64_t nrb, at::Tensor x, c10::option
 }  // namespace hipps
 
 namespace hipps {
+namespace {
+// the backward apply pass dx = a*dz + k1*x + k0 (coef = [a, k1, k0]) on the kernel form for ``unr``
+void apply_bwd_coef(hipStream_t stream, const at::Tensor& dy, const at::Tensor& x, int64_t mask_mode,
+                    const at::Tensor& scale, const at::Tensor& shift, const at::Tensor& coef, at::Tensor& dx,
+                    uint16_t* drp, const uint8_t* mbp, int64_t M, int C, int64_t unr) {
+  auto app = [&](auto kern) {
+    hipLaunchKernelGGL(kern, apply_grid(M, (int)C), kBlock, 0, stream, (const uint16_t*)dy.data_ptr(),
+                       (const uint16_t*)x.data_ptr(), nullptr, mbp, scale.data_ptr<float>(), shift.data_ptr<float>(),
+                       coef[0].data_ptr<float>(), coef[1].data_ptr<float>(), coef[2].data_ptr<float>(),
+                       (uint16_t*)dx.data_ptr(), drp, M, (int)C);
+  };
+  if (bn_pipe()) {
+    switch (mask_mode) {
+      case MASK_NONE: app(k_bn_apply_bwd<MASK_NONE, 0>); break;
+      case MASK_X: app(k_bn_apply_bwd<MASK_X, 0>); break;
+      default: app(k_bn_apply_bwd<MASK_BITS, 0>); break;
+    }
+  } else if (unr == 4) {
+    switch (mask_mode) {
+      case MASK_NONE: app(k_bn_apply_bwd<MASK_NONE, 4>); break;
+      case MASK_X: app(k_bn_apply_bwd<MASK_X, 4>); break;
+      default: app(k_bn_apply_bwd<MASK_BITS, 4>); break;
+    }
+  } else {
+    switch (mask_mode) {
+      case MASK_NONE: app(k_bn_apply_bwd<MASK_NONE>); break;
+      case MASK_X: app(k_bn_apply_bwd<MASK_X>); break;
+      default: app(k_bn_apply_bwd<MASK_BITS>); break;
+    }
+  }
+}
+}  // namespace
+}  // namespace hipps
+
+namespace hipps {
 // Backward BN whose reduction (sum dz, sum dz*x-hat per channel) was already done by the
 // producer of dy -- the 1x1 dgrad GEMM epilogue (gemm.hip, BnBwdTap): finalize + apply only,
 // i.e. one pass over dy and x instead of two.  part = f32 [2, C, nrb] channel-major partials.
@@ -942,31 +977,33 @@ void bn_backward_partials(at::Tensor part, int64_t nrb, at::Tensor dy, at::Tenso
                      (int)nrb, (int)C, M, weight.data_ptr<float>(), mean.data_ptr<float>(), invstd.data_ptr<float>(),
                      dweight.data_ptr<float>(), dbias.data_ptr<float>(), coef[0].data_ptr<float>(),
                      coef[1].data_ptr<float>(), coef[2].data_ptr<float>());
-  auto app = [&](auto kern) {
-    hipLaunchKernelGGL(kern, apply_grid(M, (int)C), kBlock, 0, stream, (const uint16_t*)dy.data_ptr(),
-                       (const uint16_t*)x.data_ptr(), nullptr, mbp, scale.data_ptr<float>(), shift.data_ptr<float>(),
-                       coef[0].data_ptr<float>(), coef[1].data_ptr<float>(), coef[2].data_ptr<float>(),
-                       (uint16_t*)dx.data_ptr(), drp, M, (int)C);
-  };
-  if (bn_pipe()) {
-    switch (mask_mode) {
-      case MASK_NONE: app(k_bn_apply_bwd<MASK_NONE, 0>); break;
-      case MASK_X: app(k_bn_apply_bwd<MASK_X, 0>); break;
-      default: app(k_bn_apply_bwd<MASK_BITS, 0>); break;
-    }
-  } else if (unr == 4) {
-    switch (mask_mode) {
-      case MASK_NONE: app(k_bn_apply_bwd<MASK_NONE, 4>); break;
-      case MASK_X: app(k_bn_apply_bwd<MASK_X, 4>); break;
-      default: app(k_bn_apply_bwd<MASK_BITS, 4>); break;
-    }
-  } else {
-    switch (mask_mode) {
-      case MASK_NONE: app(k_bn_apply_bwd<MASK_NONE>); break;
-      case MASK_X: app(k_bn_apply_bwd<MASK_X>); break;
-      default: app(k_bn_apply_bwd<MASK_BITS>); break;
-    }
+  apply_bwd_coef(stream, dy, x, mask_mode, scale, shift, coef, dx, drp, mbp, M, (int)C, unr);
+}
+
+// The apply pass alone, with the coefficients of a finalize that already ran (bn_finalize_bwd_partials):
+// dx = a*dz + k1*x + k0.  What a consumer of dx that did not produce it itself (bnconv.hip
+// bnconv_backward) runs; the same kernels, picked the same way, as bn_backward_partials.
+void bn_backward_apply(at::Tensor dy, at::Tensor x, int64_t mask_mode, at::Tensor scale, at::Tensor shift,
+                       at::Tensor coef, at::Tensor dx, int64_t C, c10::optional<at::Tensor> mask_in, int64_t unr) {
+  TORCH_CHECK(C % 8 == 0 && C <= kMaxC, "fused BN needs C % 8 == 0 and C <= 2048");
+  TORCH_CHECK(mask_mode == MASK_NONE || mask_mode == MASK_X || mask_mode == MASK_BITS, "bad mask mode");
+  TORCH_CHECK(unr == 0 || unr == 2 || unr == 4, "bn_backward_apply: unr 0 (auto), 2 or 4");
+  if (unr == 0) unr = (int64_t)x.numel() <= (int64_t(1) << 24) ? 4 : 2;
+  const int64_t M = x.numel() / C;
+  check_act(dy, "dy", M * C);
+  check_act(x, "x", M * C);
+  check_act(dx, "dx", M * C);
+  const uint8_t* mbp = nullptr;
+  if (mask_mode == MASK_BITS) {
+    TORCH_CHECK(mask_in.has_value() && mask_in->defined() && mask_in->scalar_type() == at::kByte &&
+                    mask_in->numel() == M * C / 8, "MASK_BITS needs a uint8[M*C/8] mask");
+    mbp = (const uint8_t*)mask_in->data_ptr();
   }
+  check_vec(scale, "scale", (int)C);
+  check_vec(shift, "shift", (int)C);
+  TORCH_CHECK(coef.is_cuda() && coef.scalar_type() == at::kFloat && coef.is_contiguous() && coef.numel() == 3 * C,
+              "bn_backward_apply: coef must be f32 [3, C]");
+  apply_bwd_coef(c10::hip::getCurrentHIPStream(), dy, x, mask_mode, scale, shift, coef, dx, nullptr, mbp, M, (int)C, unr);
 }
 }  // namespace hipps
 

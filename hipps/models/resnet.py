@@ -14,10 +14,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from hipps.ops.nn import (FusedBatchNorm2d, Linear, MaxPool2d, ResidualTap, bn_pro_pays, bn_relu_conv, bn_relu_conv1x1_ok,
-                          bn_relu_conv_bn, bn_relu_conv_ok, bn_relu_maxpool, conv1x1_bn_input, conv1x1_ok, conv2d,
-                          conv2d_bn, conv2d_stats, conv_bn, dual_bn_relu, dual_bn_relu_ok, global_avg_pool, materialize,
-                          stem_block, stem_block_ok)
+from hipps.ops.nn import (BNBwdLink, FusedBatchNorm2d, Linear, MaxPool2d, ResidualTap, bn_pro_pays, bn_relu_conv,
+                          bn_relu_conv1x1_ok, bn_relu_conv_bn, bn_relu_conv_ok, bn_relu_maxpool, conv1x1_bn_input,
+                          conv1x1_ok, conv2d, conv2d_bn, conv2d_stats, conv_bn, dual_bn_relu, dual_bn_relu_ok,
+                          global_avg_pool, materialize, stem_block, stem_block_ok)
 
 # One switch for the whole zoo: fused BN(+residual)(+ReLU) HIP kernels on channels-last bf16,
 # standard PyTorch elsewhere.  HIPPS_FUSED_BN=0 restores the eager MIOpen path for A/B runs.
@@ -190,9 +190,11 @@ class Bottleneck(nn.Module):
             if (bng and self.training and _FUSED_CONV and conv1x1_ok(self.conv3, x2) and
                     bn_pro_pays(self.bn2, self.conv3, x2, p2)):
                 # bn2 + ReLU in conv3's operand prologue (this layer measured faster that way)
-                x3, p3 = bn_relu_conv(self.bn2, self.conv3, x2, p2)
+                # x3 only feeds bn3: conv3's input-gradient GEMM may produce bn3's input gradient itself
+                link = BNBwdLink()
+                x3, p3 = bn_relu_conv(self.bn2, self.conv3, x2, p2, link)
                 if self.bn3._fast_ok(x3, idt):
-                    return self.bn3(x3, idt, stats=p3, res_tap=tap, defer=defer_out)
+                    return self.bn3(x3, idt, stats=p3, res_tap=tap, defer=defer_out, bwd_link=link)
                 return self.bn3(x3, idt)
             if p2 is not None and self.bn2.training and self.bn2._fast_ok(x2, None):
                 y = self.bn2(x2, stats=p2)

@@ -97,6 +97,9 @@ _STEM_QUAD = _os.environ.get("HIPPS_STEM_QUAD", "1") != "0"
 # ResNet block boundary: bn3's apply pass (+ residual + ReLU) of block i inside conv1 of block i+1
 # (csrc/bnconv.hip, DeferredApply), per layer where measured faster than the two kernels; 0: never
 _FUSED_BNCONV = _os.environ.get("HIPPS_FUSED_BNCONV", "1") != "0"
+# bn3's backward apply pass left to conv3's input-gradient GEMM, which then produces bn3's input
+# gradient as its A operand (BNBwdLink, csrc/bnconv.hip bnconv_backward)
+_FUSED_BNBWD = _os.environ.get("HIPPS_FUSED_BNBWD", "1") != "0"
 _WG_STREAMS: dict = {}
 _WG_JOINED: dict = {}  # device -> autograd graph task whose end joins the side stream
 
@@ -447,13 +450,20 @@ class _BNReluConv(torch.autograd.Function):
     kPro), the next BN's statistics in its epilogue.  The BN output is never written or re-read.
     Backward: the input-gradient GEMM with this BN's backward reduction in its epilogue (relu'
     recomputed from x), the BN backward apply, and the weight gradient with the same BN + ReLU on
-    its X tiles."""
+    its X tiles.  ``link`` (BNBwdLink, 1x1 only): the BN that consumes the output may leave its own
+    backward apply pass to this input-gradient GEMM."""
 
     @staticmethod
-    def forward(ctx, x, part, bn_w, bn_b, running_mean, running_var, eps, momentum, w_master, stride, pad):
+    def forward(ctx, x, part, bn_w, bn_b, running_mean, running_var, eps, momentum, w_master, stride, pad, link=None):
         w = bf16_weight(w_master)
         if w.dim() == 4 and w.shape[2] > 1:
             w = w.contiguous(memory_format=torch.channels_last)
+        # the next BN may leave its backward apply pass to this conv's input-gradient GEMM (BNBwdLink)
+        ctx.link = None
+        if (link is not None and _FUSED_BNBWD and _GEMM2 and w.shape[2] == 1 and stride == 1 and
+                x.shape[1] % 64 == 0 and w.shape[0] % 64 == 0 and ctx.needs_input_grad[0]):
+            link.armed = True
+            ctx.link = link
         ctx.wdtype = w_master.dtype
         ctx.wparam = w_master
         ctx.set_materialize_grads(False)
@@ -472,28 +482,49 @@ class _BNReluConv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, _dpart):
         x, w, bn_w, mean, invstd, scale, shift = ctx.saved_tensors
+        link, ctx.link = ctx.link, None
+        pend = link.take() if link is not None else None
         if dy is None:
             ctx.wparam = None
-            return (None,) * 11
+            return (None,) * 12
         s, p = ctx.geom
         dy = dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+        if pend is not None and dy.data_ptr() != pend.dx.data_ptr():
+            # the gradient did not come straight from the BN (a hook copied it): nothing has written
+            # the BN's own buffer yet -- the plain apply kernel does, and that buffer is the gradient
+            pend.apply()
+            dy, pend = pend.dx, None
         n, c, h, wd = x.shape
         cout, k = w.shape[0], w.shape[2]
         dw = None
-        if ctx.needs_input_grad[8]:
-            # the weight gradient first, on the weight-gradient side stream (as _Conv1x1 /
-            # _ConvKxK), beside the input-gradient / BN-backward chain below
+
+        def wgrad():
+            # on the weight-gradient side stream (as _Conv1x1 / _ConvKxK), beside the input-gradient /
+            # BN-backward chain
             def wg():
                 d = torch.empty(w.shape, dtype=torch.float32, device=w.device,
                                 memory_format=torch.channels_last if k > 1 else torch.contiguous_format)
                 _conv_wgrad_pro(dy, x, d, k, k, s, p, scale, shift)
                 return d if ctx.wdtype == torch.float32 else d.to(ctx.wdtype)
 
-            dw = _on_wgrad_stream(ctx.wparam, (dy, x, scale, shift), wg)
-        ctx.wparam = None
+            return _on_wgrad_stream(ctx.wparam, (dy, x, scale, shift), wg)
+
+        if ctx.needs_input_grad[8] and pend is None:
+            dw = wgrad()  # the weight gradient first
         bg = BNGradTap(x, None, mean, invstd, scale, shift)
         # gradient of the (never materialised) BN output, with that BN's backward reduction
-        if k == 1:
+        if pend is not None:
+            # dy is still unwritten: the kernel that writes it is launched first, and the weight
+            # gradient (side stream, ordered after this stream by _on_wgrad_stream) right behind it
+            def after_dx():
+                nonlocal dw
+                if ctx.needs_input_grad[8]:
+                    dw = wgrad()
+
+            wt = ctx.wt if ctx.wt is not None else w.reshape(cout, c).t().contiguous()
+            dbn = torch.empty_like(x, memory_format=torch.channels_last)
+            part = _bnbwd(pend, wt, dbn, h, wd, bg, after_dx)
+        elif k == 1:
             wt = ctx.wt if ctx.wt is not None else w.reshape(cout, c).t().contiguous()
             dbn = torch.empty_like(x, memory_format=torch.channels_last)
             part = _conv1x1_gemm(dy, wt, dbn, h, wd, 1, True, None, None, bg)
@@ -512,7 +543,8 @@ class _BNReluConv(torch.autograd.Function):
                                           None, dgw, dgb, c, None)
         else:
             native().bn_backward(dbn, x, None, MASK_X, bn_w, mean, invstd, scale, shift, dx, None, dgw, dgb, c, None)
-        return dx, None, dgw, dgb, None, None, None, None, dw, None, None
+        ctx.wparam = None
+        return dx, None, dgw, dgb, None, None, None, None, dw, None, None, None
 
 
 def bn_relu_conv_ok(bn, conv: nn.Conv2d, x: torch.Tensor) -> bool:
@@ -533,12 +565,13 @@ def bn_relu_conv_ok(bn, conv: nn.Conv2d, x: torch.Tensor) -> bool:
             (k[0] == 1 or w.is_contiguous(memory_format=torch.channels_last)))
 
 
-def bn_relu_conv(bn, conv: nn.Conv2d, x, part):
+def bn_relu_conv(bn, conv: nn.Conv2d, x, part, link=None):
     """(conv(relu(bn(x))), the next BN's statistics partials) on _BNReluConv (callers check
-    bn_relu_conv_ok; ``part``: bn's statistics partials from x's producer)."""
+    bn_relu_conv_ok; ``part``: bn's statistics partials from x's producer; ``link``: a BNBwdLink
+    that the caller also gives to the BN that consumes the result)."""
     bn._nbt_pending += 1
     return _BNReluConv.apply(x, part, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum,
-                             conv.weight, conv.stride[0], conv.padding[0])
+                             conv.weight, conv.stride[0], conv.padding[0], link)
 
 
 def bn_pro_pays(bn, conv: nn.Conv2d, x, part) -> bool:
@@ -705,6 +738,95 @@ def _bnconv_fwd(pend: DeferredApply, x, w2d, y, Hi, Wi):
     part = fused() if name == "fused" else separate()
     pend.done = True
     return part
+
+
+class BNBwdLink:
+    """Joins a 1x1 conv to the fused BN that consumes its output (ResNet conv3 -> bn3), so that the
+    BN's backward apply pass -- dx3 = a * dz + k1 * x3 + k0, the widest tensor of the block,
+    written and read straight back by the conv's input-gradient GEMM -- can run inside that GEMM
+    (csrc/bnconv.hip bnconv_backward).  The function that calls both creates one link and gives it
+    to both autograd Functions.  The conv's forward arms it when its backward will run the stride-1
+    1x1 input-gradient GEMM on the hipps cores.  The BN's backward, on an armed link, only runs its
+    finalize (dgamma, dbeta, the coefficients), allocates dx3, parks a PendingBNBwd here and returns
+    dx3 unwritten; the conv's backward, which autograd runs next on that very buffer, takes the
+    record and writes dx3 before anything reads it -- in the fused kernel, or with the plain apply
+    kernel first.  The tensor between the two must have no other reader, and a gradient hook on it
+    may copy the gradient but not change it: a gradient that arrives in another buffer is replaced
+    by the BN's own, written by the plain kernel."""
+
+    __slots__ = ("armed", "pend")
+
+    def __init__(self):
+        self.armed = False
+        self.pend = None
+
+    def take(self):
+        pend, self.pend = self.pend, None
+        return pend
+
+
+class PendingBNBwd:
+    """A fused BN's backward apply pass that has not run: dx = a * dz + k1 * x + k0 with dz = dy where
+    the BN's ReLU bit is set, coef = [a, k1, k0] from the finalize that has run."""
+
+    __slots__ = ("dy", "x", "mask", "scale", "shift", "coef", "dx")
+
+    def __init__(self, dy, x, mask, scale, shift, coef, dx):
+        self.dy, self.x, self.mask, self.scale, self.shift, self.coef, self.dx = dy, x, mask, scale, shift, coef, dx
+
+    def apply(self):
+        native().bn_backward_apply(self.dy, self.x, MASK_BITS, self.scale, self.shift, self.coef, self.dx,
+                                   self.x.shape[1], self.mask)
+
+
+def _bnbwd_tile(plain, N: int) -> int:
+    """The column tile (64 / 128) at which the fused backward kernel gives the bits of the recorded
+    input-gradient pick ``plain``, or 0 if it cannot.  Its rows are split like gemm2's 128-row
+    tiles; the BN-backward epilogue reduces the stored bf16 tile with one thread layout per column
+    tile width in both cores, whatever the wave split, so the first core ("g1": 128 wide where that
+    divides N, else 64) has a twin too (tests/test_bnbwd_gpu.py)."""
+    if plain is None:
+        return 0
+    if plain == "g1":
+        return 128 if N % 128 == 0 else 64
+    bm, bn, _ = _g2_parse(plain)
+    return bn if bm == 128 and bn in (64, 128) else 0
+
+
+def _bnbwd(pend: PendingBNBwd, wt, dbn, Hi, Wi, bg, after_dx):
+    """conv3's input gradient on a gradient buffer whose producer, bn3's backward apply pass, is still
+    pending: writes pend.dx and dbn = pend.dx . wt^T, returns the backward reduction partials of the
+    BN ``bg`` (BNGradTap) whose output gradient dbn is.  Two routes, chosen per shape by measurement
+    on the real operands (tuner kind 'bnbwd'): "separate" = the apply kernel + the tuned 1x1 GEMM,
+    "fused" = one kernel (bnconv.hip).  bn3's finalize precedes both and is not timed.  The fused
+    kernel is offered only at the tile of the shape's recorded 1x1 pick (_bnbwd_tile), so both
+    routes give the same bits and the choice cannot change a result.  ``after_dx()`` is called once
+    the kernel that writes pend.dx has been launched (the weight gradient reads it)."""
+    C = native()
+    N, K = wt.shape
+    M = dbn.numel() // N
+
+    def separate(cb=None):
+        pend.apply()
+        if cb is not None:
+            cb()
+        return _conv1x1_gemm(pend.dx, wt, dbn, Hi, Wi, 1, True, None, None, bg)
+
+    def fused(bn, cb=None):
+        part = torch.empty((2, N, C.bnconv_mtiles(M)), dtype=torch.float32, device=dbn.device)
+        C.bnconv_backward(pend.dy, pend.x, pend.mask, pend.coef, wt, pend.dx, dbn, part, bg.x, bg.mean, bg.invstd,
+                          bg.scale, bg.shift, bn)
+        if cb is not None:
+            cb()
+        return part
+
+    # (the first call for a shape runs the separate route, which measures the plain GEMM's pick)
+    bn = _bnbwd_tile(TUNER.cache.get(("1x1", M, K, N, 1, Hi, Wi, (True, False, False, False, True, False))), N)
+    name = "separate"
+    if bn:
+        name = TUNER.pick(("bnbwd", M, K, N), ["separate", "fused"],
+                          lambda n: fused(bn) if n == "fused" else separate())
+    return fused(bn, after_dx) if name == "fused" else separate(after_dx)
 
 
 _SHADOWS: list = []  # [fp32 flat param buffer, bf16 shadow] pairs (FlatStore.enable_bf16_shadow)
@@ -2331,7 +2453,7 @@ def conv1x1_stats(x, weight, stride=1, tap=None, alias=False, bngrad=None, s2tap
 class _FusedBNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, res, weight, bias, running_mean, running_var, eps, momentum, relu, part=None, tap=None,
-                defer=False):
+                defer=False, link=None):
         C = x.shape[1]
         y = torch.empty_like(x, memory_format=torch.channels_last)
         f32 = dict(dtype=torch.float32, device=x.device)
@@ -2356,6 +2478,8 @@ class _FusedBNAct(torch.autograd.Function):
         # the residual gradient is dy * bits (or dy): hand it to the consumer through the tap
         ctx.tap = tap if (res is not None and mode in (MASK_NONE, MASK_BITS)) else None
         ctx.save_for_backward(x, mask, weight, mean, invstd, scale, shift)
+        # x's producer may run this BN's backward apply pass inside its input-gradient GEMM (BNBwdLink)
+        ctx.link = link if (link is not None and link.armed and mode == MASK_BITS) else None
         # a consuming 1x1 conv may reduce this BN's backward statistics for it (BNGradTap)
         ctx.bngrad = None
         if mode in (MASK_X, MASK_BITS):
@@ -2373,7 +2497,15 @@ class _FusedBNAct(torch.autograd.Function):
         dw = torch.empty_like(weight)
         db = torch.empty_like(weight)
         bg, ctx.bngrad = ctx.bngrad, None
-        if bg is not None and bg.part is not None:  # reduction already done in the consumer's epilogue
+        link, ctx.link = ctx.link, None
+        if link is not None and bg is not None and bg.part is not None and dres is None:
+            # finalize only: x's producer writes dx in (or right before) its input-gradient GEMM
+            coef = torch.empty((3, ctx.C), dtype=torch.float32, device=x.device)
+            native().bn_finalize_bwd_partials(bg.part, bg.part.shape[2], x.numel() // ctx.C, weight, mean, invstd, dw,
+                                              db, coef)
+            bg.part = None
+            link.pend = PendingBNBwd(dy, x, mask, scale, shift, coef, dx)
+        elif bg is not None and bg.part is not None:  # reduction already done in the consumer's epilogue
             native().bn_backward_partials(bg.part, bg.part.shape[2], dy, x, ctx.mode, weight, mean, invstd, scale,
                                           shift, dx, dres, dw, db, ctx.C, mask)
             bg.part = None
@@ -2382,7 +2514,7 @@ class _FusedBNAct(torch.autograd.Function):
                                  mask)
         if tap is not None:
             tap.dy, tap.mask = dy, (mask if ctx.mode == MASK_BITS else None)
-        return dx, dres, dw, db, None, None, None, None, None, None, None, None
+        return dx, dres, dw, db, None, None, None, None, None, None, None, None, None
 
 
 class _DualBNRelu(torch.autograd.Function):
@@ -2481,15 +2613,15 @@ def _take_pending(x, stride):
 
 
 def fused_bn_act(x, weight, bias, running_mean, running_var, eps=1e-5, momentum=0.1, relu=True, residual=None,
-                 part=None, res_tap=None, defer=False):
+                 part=None, res_tap=None, defer=False, bwd_link=None):
     """Training-mode BN (+residual) (+ReLU) on a channels-last bf16 HIP tensor.  ``part``: the
     [2, C, nrb] partial statistics when the producer (conv1x1_stats) already reduced them.
     ``res_tap``: an armed ResidualTap -- the residual's gradient goes to its consumer instead
     of autograd (the residual input then receives no gradient from this op).  ``defer`` (with
     ``part``, a residual and ReLU): finalize only, the apply pass is left to the consumer
-    (DeferredApply)."""
+    (DeferredApply).  ``bwd_link``: the BNBwdLink also given to the conv that produced x."""
     return _FusedBNAct.apply(x, residual, weight, bias, running_mean, running_var, eps, momentum, relu, part,
-                             res_tap, bool(defer) and _FUSED_BNCONV)
+                             res_tap, bool(defer) and _FUSED_BNCONV, bwd_link)
 
 
 class FusedBatchNorm2d(nn.BatchNorm2d):
@@ -2528,13 +2660,13 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
             return False
         return True
 
-    def forward(self, x, residual=None, stats=None, res_tap=None, defer=False):
+    def forward(self, x, residual=None, stats=None, res_tap=None, defer=False, bwd_link=None):
         if self._fast_ok(x, residual):
             if self.training:
                 self._nbt_pending += 1
                 tap = res_tap if (res_tap is not None and res_tap.armed and residual is not None) else None
                 return fused_bn_act(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
-                                    self.momentum, self.relu, residual, stats, tap, defer)
+                                    self.momentum, self.relu, residual, stats, tap, defer, bwd_link)
             if not torch.is_grad_enabled() or not (x.requires_grad or (residual is not None and
                                                                        residual.requires_grad)):
                 scale = self.weight / torch.sqrt(self.running_var + self.eps)
